@@ -1,7 +1,7 @@
 """bench.py -- BASELINE.json metric on MI355X: decode tokens/s (+ prefill TFLOP/s) of Llama-3-8B fp8 (w8a8),
 batch 32 x seq 2048, synthetic random weights and token ids, every device op a hand-written HIP kernel.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1 without a launcher: this process starts the N ranks itself, one per GPU, as bench_one_batch.py:527-546 spawns one
      process per tp_rank, and relays rank 0's JSON line; under `python -m torch.distributed.run --nproc-per-node N ... bench.py
      --gpus N ...` the launcher's RANK / LOCAL_RANK / WORLD_SIZE are used and must agree with --gpus)
@@ -11,7 +11,14 @@ filled by a real prefill of 32 x 2048 tokens, index tensors) are resident in HBM
 Prints ONE JSON line (rank 0).  N > 1 shards the model tensor-parallel exactly like the reference
 (linear.py / llama.py:118-133) with one RCCL all-reduce per row-parallel layer: strong scaling of the same batch.
 
-Extra objects on the line:
+A plain run does what the headline figure needs and no more: set-up, ONE prefill of the prompts (it fills the KV pool; its time is
+reported as prefill.warm = false, first-launch costs included), graph capture, W warm-up steps, K timed steps, the JSON line.
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/logits.npy (float32 [batch, vocab]; a seeded
+column sample when that would exceed 48 MB) and DIR/next_token_ids.npy (float64 [batch]); every input is seeded, so two builds run
+with the same arguments can be compared output for output.
+
+--full adds the measurements that take runs of their own: an untimed warm-up prefill before the timed one (prefill.warm = true:
+the steady-state prefill TFLOP/s) and these objects on the line:
   roofline     dominant kernel = decode_attn_stage1 (KV stream).  achieved = algorithmic KV bytes of one launch
                (bs * seq * Hkv * D * 2 B * 2) / mean launch duration measured here with HIP events on the launch stream.
   cpu_baseline the oracle's torch-native restatement timed on this box's host cores on a bounded sample
@@ -34,6 +41,11 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=32)
     ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (logits, greedy next-token ids) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the warm-up prefill (steady-state prefill TFLOP/s), the "
+                         "dominant-kernel roofline probe and the CPU baseline")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--seq-len", type=int, default=2048)
     ap.add_argument("--model", default="llama3-8b", choices=["llama3-8b", "llama3-70b", "qwen2-7b", "tiny"])
@@ -52,7 +64,7 @@ def parse_args():
     ap.add_argument("--allow-eager", action="store_true",
                     help="if the HIP-graph capture of the decode step fails, time eager (launch-bound) steps and say so in the metric "
                          "name instead of exiting with code 3")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU leg")
     ap.add_argument("--no-fused-decode", action="store_true", help="measurement hook: the per-op decode path (same logits, more launches)")
     ap.add_argument("--prefill-chunk", type=int, default=32,
                     help="requests per prefill call (32 = the whole BASELINE batch in one extend, as bench_one_batch.py does; "
@@ -85,6 +97,8 @@ def parse_args():
                     help="ONE process builds rank 0's shard of a tp-N model and replaces each collective by a same-size device copy: "
                          "per-rank compute ms/step without communication (TP-readiness measurement on a 1-GPU box; not the metric)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps needs at least 1 timed step, --warmup at least 0")
     preset = {2: dict(model="llama3-8b", quant="none", batch=32, seq_len=2048),
               3: dict(model="llama3-8b", quant="w8a8_fp8", batch=64, seq_len=2048, shared_prefix=1536),
               4: dict(model="qwen2-7b", quant="awq", batch=32, seq_len=1024, dtype="f16"),
@@ -96,6 +110,24 @@ def parse_args():
     if args.shared_prefix and not (0 < args.shared_prefix < args.seq_len and args.seq_dist == "uniform"):
         ap.error("--shared-prefix P needs 0 < P < --seq-len and uniform lengths")
     return args
+
+
+DUMP_LOGITS_BYTES = 48 << 20   # --dump-outputs: float32 logits above this are written as a seeded sample of their columns
+
+
+def dump_outputs(out_dir, logits, next_ids):
+    """--dump-outputs: the last timed step's return value, logits [batch, vocab] -> float32 and the greedy ids -> float64."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    lg = logits.detach().float().cpu().numpy()
+    max_cols = DUMP_LOGITS_BYTES // (4 * max(1, lg.shape[0]))
+    if lg.shape[1] > max_cols:
+        cols = np.sort(np.random.RandomState(0).choice(lg.shape[1], max_cols, replace=False))
+        np.save(os.path.join(out_dir, "logits_columns.npy"), cols.astype(np.float64))
+        lg = lg[:, cols]
+    np.save(os.path.join(out_dir, "logits.npy"), np.ascontiguousarray(lg, dtype=np.float32))
+    np.save(os.path.join(out_dir, "next_token_ids.npy"), next_ids.detach().cpu().numpy().astype(np.float64))
 
 
 def config1_cpu_plumbing(args):
@@ -120,7 +152,9 @@ def config1_cpu_plumbing(args):
                "layers": [{"ln1": torch.ones(hid).bfloat16(), "ln2": torch.ones(hid).bfloat16(),
                            "qkv": w(3 * hq * d, hid) + (None,), "o": w(hid, hq * d), "gate_up": w(2 * inter, hid), "down": w(hid, inter)}
                           for _ in range(cfg.num_hidden_layers)]}
-    prompt, steps = 128, max(1, min(args.steps, 16))
+    prompt, steps = 128, args.steps
+    if prompt + steps + 2 > cfg.max_position_embeddings:
+        raise SystemExit(f"[bench] --config 1: --steps {steps} exceeds the network's {cfg.max_position_embeddings} positions")
     m = OracleLlama(cfg, weights, torch.bfloat16, False, prompt + steps + 2)
     r2t = torch.arange(1, prompt + steps + 2, dtype=torch.int32).view(1, -1)
     rpi, ids = torch.zeros(1, dtype=torch.int64), torch.randint(0, 10000, (prompt,), generator=g)
@@ -133,6 +167,8 @@ def config1_cpu_plumbing(args):
         logits = m.forward(nxt, seq - 1, r2t, rpi, seq, r2t[0, seq[0] - 1].view(1).long())
         nxt = logits[-1:].float().argmax(-1)
     dt = (time.perf_counter() - t0) / steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, logits[-1:], nxt)
     print(json.dumps({"metric": "decode tokens/sec, OPT-125m-sized network, greedy, batch 1, torch-native attention on the CPU (BASELINE configs[0]: plumbing, no GPU)",
                       "value": 1.0 / dt, "unit": "tokens/s", "n_gpus": 0, "steps": steps, "warmup": 0, "ms_per_step": dt * 1e3, "higher_is_better": True,
                       "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
@@ -510,9 +546,11 @@ def main():
     # untimed warm-up prefill, undone: the SAME calls at full length (bench_one_batch.py warms up with the batch it then measures) --
     # it loads every prefill kernel's code object, sets the LDS attributes, and lets the caching allocator obtain the multi-GB
     # activation buffers once.  (Round 4: with a 512-token warm-up the timed prefill made those first hipMallocs itself; one run of
-    # the round read 0.677 s where the runs around it read 0.46 s.)
-    prefill_all()
-    torch.cuda.synchronize()
+    # the round read 0.677 s where the runs around it read 0.46 s.)  Only under --full: the decode steps do not need it, and without
+    # it the one prefill below is reported as a cold one (prefill.warm = false).
+    if args.full:
+        prefill_all()
+        torch.cuda.synchronize()
     runner.clear()
     # the allocator hands out consecutive slots; a random permutation of the free list makes the gather non-contiguous
     alloc = runner.token_to_kv_pool_allocator
@@ -589,7 +627,8 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        next_ids = K_argmax(step_fn(state, next_ids))
+        logits = step_fn(state, next_ids)
+        next_ids = K_argmax(logits)
     barrier()
     elapsed = time.perf_counter() - t0
     if not (int(next_ids.min()) >= 0 and int(next_ids.max()) < cfg.vocab_size):
@@ -608,66 +647,79 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # ---- dominant kernel: decode attention stage 1, HIP-event timed on the launch stream over all layers' pools ----
-    from ltp_sglang_amd import sgl_kernel as K
-
-    cur_seq = state.seq_lens_cpu[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, logits, next_ids)   # (graph replay: `logits` is the graph's output buffer, not replayed since)
+        phase("dump_outputs")
     md = runner.attn_backend.forward_metadata
-    hq_r, hkv_r = hq // tp, max(1, hkv // tp)
-    qd = torch.randn(bs, hq_r, d, device=dev).to(runner.dtype)
-    pool = runner.token_to_kv_pool
-    evs = []
-    be = runner.attn_backend
-    fp8_lin = quant in ("w8a8_fp8", "fp8")
-    in_launch_merge = d in (64, 128) and hq_r * d <= 16384 and (
-        (fp8_lin and runner.model.fused_decode and runner.model.fused_attn_merge) or (not fp8_lin and be.merge_in_launch))
-    kscale, vscale = runner.model.layers[0].self_attn.kv_scales()
-    kscale, vscale = (float(kscale) if kscale is not None else 1.0), (float(vscale) if vscale is not None else 1.0)
-    for rep in range(3):
-        for l in range(L):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            if md.cascade_prefix_indices is not None:
-                # the launch pair the captured step runs over a shared prefix: prefix once for all requests + private suffixes, merged
-                K.decode_attention_cascade(qd, pool.get_key_buffer(l), pool.get_value_buffer(l), md.cascade_prefix_indices,
-                                           md.cascade_prefix_splits, md.kv_indptr, md.kv_indices, md.attn_logits, md.attn_lse,
-                                           md.num_kv_splits, be.max_kv_splits, d ** -0.5, be._merge_counter_buf(qd), 0.0, kscale, vscale,
-                                           want_o=not fp8_lin, want_quant=fp8_lin)
-            elif in_launch_merge:
-                # the launch the captured step runs: stage 1 + the stage-2 merge + per-token fp8 quant of the merged rows by each
-                # request's last workgroup (r3's probe timed stage 1 alone, a cheaper launch than the step's)
-                K.decode_attention_merge_quant(qd, pool.get_key_buffer(l), pool.get_value_buffer(l), md.kv_indptr, md.kv_indices,
-                                               md.attn_logits, md.attn_lse, md.num_kv_splits, be.max_kv_splits, d ** -0.5,
-                                               be._merge_counter_buf(qd), 0.0, kscale, vscale, want_o=not fp8_lin, want_quant=fp8_lin,
-                                               sched=md.sched)
-            else:
-                # o = None: stage 1 only (the split partials)
-                K.decode_attention_fwd(qd, pool.get_key_buffer(l), pool.get_value_buffer(l), None, md.kv_indptr, md.kv_indices,
-                                       md.attn_logits, md.attn_lse, md.num_kv_splits, be.max_kv_splits, d ** -0.5)
-            e1.record()
-            evs.append((e0, e1))
-    torch.cuda.synchronize()
-    attn_ms = sorted(a.elapsed_time(b) for a, b in evs[L:])  # first sweep = warm-up
-    attn_ms = sum(attn_ms) / len(attn_ms)
-    # algorithmic bytes: K and V rows of every DISTINCT cached token (a shared prefix is counted once: what a perfect kernel reads)
-    kv_rows = float(sum(state.seq_lens_cpu)) - (bs - 1) * P
-    kv_bytes = kv_rows * hkv_r * d * 2 * kv_es
-    achieved = kv_bytes / (attn_ms * 1e-3) / 1e9
+    hkv_r = max(1, hkv // tp)
 
-    phase("roofline_probe")
+    def roofline_probe():
+        """--full, every rank: the dominant kernel, decode attention stage 1, HIP-event timed on the launch stream over all layers'
+        pools.  Returns the `roofline` object of the line."""
+        from ltp_sglang_amd import sgl_kernel as K
+
+        hq_r = hq // tp
+        qd = torch.randn(bs, hq_r, d, device=dev).to(runner.dtype)
+        pool = runner.token_to_kv_pool
+        evs = []
+        be = runner.attn_backend
+        fp8_lin = quant in ("w8a8_fp8", "fp8")
+        in_launch_merge = d in (64, 128) and hq_r * d <= 16384 and (
+            (fp8_lin and runner.model.fused_decode and runner.model.fused_attn_merge) or (not fp8_lin and be.merge_in_launch))
+        kscale, vscale = runner.model.layers[0].self_attn.kv_scales()
+        kscale, vscale = (float(kscale) if kscale is not None else 1.0), (float(vscale) if vscale is not None else 1.0)
+        for rep in range(3):
+            for l in range(L):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                if md.cascade_prefix_indices is not None:
+                    # the launch pair the captured step runs over a shared prefix: prefix once for all requests + private suffixes, merged
+                    K.decode_attention_cascade(qd, pool.get_key_buffer(l), pool.get_value_buffer(l), md.cascade_prefix_indices,
+                                               md.cascade_prefix_splits, md.kv_indptr, md.kv_indices, md.attn_logits, md.attn_lse,
+                                               md.num_kv_splits, be.max_kv_splits, d ** -0.5, be._merge_counter_buf(qd), 0.0, kscale, vscale,
+                                               want_o=not fp8_lin, want_quant=fp8_lin)
+                elif in_launch_merge:
+                    # the launch the captured step runs: stage 1 + the stage-2 merge + per-token fp8 quant of the merged rows by each
+                    # request's last workgroup (r3's probe timed stage 1 alone, a cheaper launch than the step's)
+                    K.decode_attention_merge_quant(qd, pool.get_key_buffer(l), pool.get_value_buffer(l), md.kv_indptr, md.kv_indices,
+                                                   md.attn_logits, md.attn_lse, md.num_kv_splits, be.max_kv_splits, d ** -0.5,
+                                                   be._merge_counter_buf(qd), 0.0, kscale, vscale, want_o=not fp8_lin, want_quant=fp8_lin,
+                                                   sched=md.sched)
+                else:
+                    # o = None: stage 1 only (the split partials)
+                    K.decode_attention_fwd(qd, pool.get_key_buffer(l), pool.get_value_buffer(l), None, md.kv_indptr, md.kv_indices,
+                                           md.attn_logits, md.attn_lse, md.num_kv_splits, be.max_kv_splits, d ** -0.5)
+                e1.record()
+                evs.append((e0, e1))
+        torch.cuda.synchronize()
+        attn_ms = sorted(a.elapsed_time(b) for a, b in evs[L:])  # first sweep = warm-up
+        attn_ms = sum(attn_ms) / len(attn_ms)
+        # algorithmic bytes: K and V rows of every DISTINCT cached token (a shared prefix is counted once: what a perfect kernel reads)
+        kv_rows = float(sum(state.seq_lens_cpu)) - (bs - 1) * P
+        kv_bytes = kv_rows * hkv_r * d * 2 * kv_es
+        achieved = kv_bytes / (attn_ms * 1e-3) / 1e9
+        # HBM traffic of the dominant kernel: PMC counters cannot be read from inside the process, so the per-launch figure
+        # comes from the newest committed summary of a `rocprofv3 --pmc` pass over this same command (tools/profile_round.sh,
+        # tools/pmc_traffic.py), together with the git SHA that profile was taken at
+        traffic, traffic_src, traffic_sha = None, None, None
+        if (args.model, args.quant, bs, seq, world, args.kv_cache_dtype, args.emulate_tp) == ("llama3-8b", "w8a8_fp8", 32, 2048, 1, "auto", 0):
+            pmc_rel, pmc = _traffic_profile()
+            k1 = (pmc or {}).get("kernels", {}).get("decode_attn_stage1", {})
+            if "fetch_bytes_per_launch" in k1:
+                traffic = k1["fetch_bytes_per_launch"] + k1.get("write_bytes_per_launch", 0.0)
+                traffic_src = f"{pmc_rel} (rocprofv3 --pmc FETCH_SIZE, WRITE_SIZE; FETCH_SIZE x2 on gfx950)"
+                traffic_sha = pmc.get("git_sha")
+        return {"kernel": "decode_attn_stage1" + (" (+ in-launch stage-2 merge + fp8 quant, the launch the step runs)" if in_launch_merge else " (stage 1 only)"),
+                "bound": "hbm", "achieved": achieved, "peak": 8000.0,
+                "unit": "GB/s", "frac": achieved / 8000.0, "traffic": traffic,
+                "traffic_source": traffic_src, "traffic_profile_git_sha": traffic_sha, "launch_us": attn_ms * 1e3, "algorithmic_bytes_per_launch": kv_bytes}
+
+    roofline = None
+    if args.full:
+        roofline = roofline_probe()
+        phase("roofline_probe")
     if rank != 0:
         return
-    # HBM traffic of the dominant kernel: PMC counters cannot be read from inside the process, so the per-launch figure
-    # comes from the newest committed summary of a `rocprofv3 --pmc` pass over this same command (tools/profile_round.sh,
-    # tools/pmc_traffic.py), together with the git SHA that profile was taken at
-    traffic, traffic_src, traffic_sha = None, None, None
-    if (args.model, args.quant, bs, seq, world, args.kv_cache_dtype, args.emulate_tp) == ("llama3-8b", "w8a8_fp8", 32, 2048, 1, "auto", 0):
-        pmc_rel, pmc = _traffic_profile()
-        k1 = (pmc or {}).get("kernels", {}).get("decode_attn_stage1", {})
-        if "fetch_bytes_per_launch" in k1:
-            traffic = k1["fetch_bytes_per_launch"] + k1.get("write_bytes_per_launch", 0.0)
-            traffic_src = f"{pmc_rel} (rocprofv3 --pmc FETCH_SIZE, WRITE_SIZE; FETCH_SIZE x2 on gfx950)"
-            traffic_sha = pmc.get("git_sha")
     tok_s = bs * args.steps / elapsed
     weights_bytes = lin_params * (1 if quant in ("w8a8_fp8", "fp8") else (0.5 if quant == "awq" else 2)) + ranks_run * (V // tp) * hid * 2
     step_bytes = weights_bytes + ranks_run * (kv_tokens + bs * (args.warmup + args.steps / 2)) * L * 2 * hkv_s * d * kv_es
@@ -693,14 +745,11 @@ def main():
                    "act_dtype": args.dtype},
         "prefill": {"tflops": prefill_flops / prefill_s / 1e12, "seconds": prefill_s, "tokens": sum(new_tok), "prompt_tokens": sum(lens),
                     "tokens_per_s": sum(new_tok) / prefill_s, "prompt_tokens_per_s": sum(lens) / prefill_s, "flops": prefill_flops,
-                    "requests_per_extend_call": min(bs, args.prefill_chunk)},
+                    "requests_per_extend_call": min(bs, args.prefill_chunk), "warm": bool(args.full)},
         "step_roofline": {"algorithmic_bytes_per_step": step_bytes, "hbm_peak_GBps": 8000.0,
                           "ranks_counted": ranks_run,
                           "frac_of_hbm_roofline": step_bytes / (elapsed / args.steps) / (8e12 * ranks_run)},
-        "roofline": {"kernel": "decode_attn_stage1" + (" (+ in-launch stage-2 merge + fp8 quant, the launch the step runs)" if in_launch_merge else " (stage 1 only)"),
-                     "bound": "hbm", "achieved": achieved, "peak": 8000.0,
-                     "unit": "GB/s", "frac": achieved / 8000.0, "traffic": traffic,
-                     "traffic_source": traffic_src, "traffic_profile_git_sha": traffic_sha, "launch_us": attn_ms * 1e3, "algorithmic_bytes_per_launch": kv_bytes},
+        "roofline": roofline,   # (None without --full)
     }
     # what the split rule made of the batch (SURVEY 7 hard-part (d): split-KV balance under raggedness)
     sp = md.num_kv_splits[:bs].cpu().tolist()
@@ -709,9 +758,10 @@ def main():
     if md.sched is not None:   # sorted unit list: {T, units, total tokens, capacity}
         hdr = md.sched[:4].cpu().tolist()
         out["kv_splits"].update({"split_tokens": hdr[0], "list_units": hdr[1], "list_capacity": hdr[3], "rounds_pct": args.kv_sched_rounds_pct})
-    if not args.no_cpu_baseline and args.model != "tiny" and world == 1 and args.emulate_tp <= 1 and args.config in (0,):  # rank 0 at N = 1 only; the headline run
-        out["cpu_baseline"] = cpu_baseline_sample(cfg, bs, seq, L)
-    phase("cpu_baseline")
+    if args.full:
+        if not args.no_cpu_baseline and args.model != "tiny" and world == 1 and args.emulate_tp <= 1 and args.config in (0,):  # rank 0 at N = 1 only; the headline run
+            out["cpu_baseline"] = cpu_baseline_sample(cfg, bs, seq, L)
+        phase("cpu_baseline")
     out["phases_s"] = phases
     print(json.dumps(out))
 

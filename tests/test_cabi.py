@@ -112,7 +112,8 @@ def test_fp8_gemm_kernel_choice_and_k_partition_are_host_logic(pkg):
     t = _cabi.lib.sgl_mi355_fp8_gemm_tile_choice
     want_t = {(64 + 1, 4096, 4096): 1, (256, 28672, 4096): 1, (1024, 4096, 14336): 1, (1024, 4096, 4096): 1,
               (2048, 4096, 4096): 2, (2048, 4096, 14336): 2, (1536, 4096, 4096): 2, (1024, 6144, 4096): 2, (8192, 1024, 8192): 2,
-              (4096, 6144, 4096): 2, (520, 8192, 8192): 2,
+              (520, 8192, 8192): 2,
+              (4096, 6144, 4096): 0,   # two rounds of 256x256 tiles at 46 us = 92 against three of 256x128 at 31 us = 93 (tiled_gemm.hip choose_tile)
               (2048, 6144, 4096): 0, (2048, 28672, 4096): 0, (4096, 4096, 4096): 0, (8192, 6144, 4096): 0,
               (65536, 28672, 4096): 0, (65536, 4096, 14336): 0, (2048, 4096, 4000): 0}
     got_t = {k: int(t(k[0], k[1], k[2], ws)) for k in want_t}

@@ -10,7 +10,7 @@ cd "$R"
 VARIANT=$(readlink -f "$1"); shift
 for v in base variant base variant; do
   if [ $v = base ]; then unset SGL_MI355_LIB; else export SGL_MI355_LIB="$VARIANT"; fi
-  timeout -k 10 500 python bench.py --no-cpu-baseline --steps 16 "$@" > /tmp/ab.log 2>&1
+  timeout -k 10 500 python bench.py --full --no-cpu-baseline --steps 16 "$@" > /tmp/ab.log 2>&1
   python - $v <<'PY'
 import json, sys
 d = json.loads(open("/tmp/ab.log").read().strip().splitlines()[-1])

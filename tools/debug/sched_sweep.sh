@@ -4,7 +4,7 @@ set -u
 OUT=gpurun_out/r5_sched_sweep.log
 : > $OUT
 run() {
-  timeout -k 10 300 python bench.py "$@" --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
+  timeout -k 10 300 python bench.py "$@" --full --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 r=d['roofline']; k=d.get('kv_splits',{})

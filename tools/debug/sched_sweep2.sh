@@ -4,7 +4,7 @@ set -u
 OUT=gpurun_out/r5_sched_sweep2.log
 : > $OUT
 run() {
-  timeout -k 10 300 python bench.py "$@" --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
+  timeout -k 10 300 python bench.py "$@" --full --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']
 print('$*', '|', round(d['value'],1),'tok/s', round(d['ms_per_step'],4),'ms', 'attn_us', round(r['launch_us'],2))" >> $OUT 2>&1 || echo "$* FAILED" >> $OUT

@@ -5,9 +5,9 @@ other than --kernel-trace):
 
     cd /tmp && export TMPDIR=/tmp
     rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $R/gpurun_out/pmc_fetch -o pmc -- \
-        python3 $R/bench.py --steps 2 --warmup 1 --no-graph --no-cpu-baseline
+        python3 $R/bench.py --full --steps 2 --warmup 1 --no-graph --no-cpu-baseline
     rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $R/gpurun_out/pmc_write -o pmc -- \
-        python3 $R/bench.py --steps 2 --warmup 1 --no-graph --no-cpu-baseline
+        python3 $R/bench.py --full --steps 2 --warmup 1 --no-graph --no-cpu-baseline
     python3 $R/tools/pmc_traffic.py $R/gpurun_out/pmc_fetch $R/gpurun_out/pmc_write > $R/gpurun_out/pmc_traffic.json
 
 Corrections (MI355X_MICROARCH.md, "HBM [CDNA4]"): FETCH_SIZE / WRITE_SIZE are reported in KiB-like units of 1024 B by

@@ -7,7 +7,9 @@ cd "$R"
 TAG=${1:-r5}
 OUT=gpurun_out/${TAG}_configs.jsonl
 : > $OUT
-run() { echo "== bench.py $*" >&2; timeout -k 10 900 python bench.py --steps 16 --no-cpu-baseline "$@" 2> gpurun_out/${TAG}_configs_last.err | tail -1 >> $OUT || { echo "FAILED: bench.py $*" >&2; tail -5 gpurun_out/${TAG}_configs_last.err >&2; }; }
+ERR=${OUT%.jsonl}_last.err
+# --full: the summary below prints the attention launch's roofline figures and the steady-state prefill TFLOP/s
+run() { echo "== bench.py $*" >&2; timeout -k 10 900 python bench.py --full --steps 16 --no-cpu-baseline "$@" 2> $ERR | tail -1 >> $OUT || { echo "FAILED: bench.py $*" >&2; tail -5 $ERR >&2; }; }
 timeout -k 10 300 python bench.py --config 1 --steps 8 | tail -1 >> $OUT
 run --config 2
 run --config 3
