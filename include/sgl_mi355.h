@@ -445,6 +445,16 @@ int sgl_mi355_awq_set_exact_weights(int on);
 int sgl_mi355_awq_gemm(const void* x, int64_t x_stride_elems, const void* qpacked, const void* sz, void* y,
                        int64_t y_stride_elems, const void* bias, int M, int N, int K, int group_size, int dtype,
                        float* workspace, int64_t workspace_floats, void* stream);
+/* The same product for M > 64 (AWQLinearMethod.apply, awq.py:401-418, at prefill and large-batch decode sizes): the M dimension
+ * is tiled (128 rows x 128 columns per workgroup), the int4 image is dequantised in registers into MFMA B operands, X goes
+ * through LDS; weight values bit-identical to sgl_mi355_awq_dequantize's for bf16 and f16.  Arguments as sgl_mi355_awq_gemm;
+ * workspace: kranges x M x N floats when sgl_mi355_awq_gemm_tiled_kranges(M, N, K) > 1.  Allocation- and sync-free. */
+int sgl_mi355_awq_gemm_tiled(const void* x, int64_t x_stride_elems, const void* qpacked, const void* sz, void* y,
+                             int64_t y_stride_elems, const void* bias, int M, int N, int K, int group_size, int dtype,
+                             float* workspace, int64_t workspace_floats, void* stream);
+/* split-K ranges of sgl_mi355_awq_gemm_tiled (awq.py:401-418 has no counterpart: the reference's matmul picks its own split):
+ * whole 128-k blocks, at least three per range, the count that minimises MFMA time + slab traffic; 1: no workspace */
+int sgl_mi355_awq_gemm_tiled_kranges(int M, int N, int K);
 /* Producer half of the launch-boundary split-K reduce for an int4 weight: raw f32 partial sums [kranges, M, N]
  * (kranges = sgl_mi355_awq_gemm_num_kranges(M, K)); consumed by sgl_mi355_fused_add_rmsnorm_quant_fp8 (slabs, no scales). */
 int sgl_mi355_awq_gemm_slabs(const void* x, int64_t x_stride_elems, const void* qpacked, const void* sz, float* slabs, int M,

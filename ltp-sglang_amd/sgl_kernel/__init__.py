@@ -42,6 +42,7 @@ from .gemm import (
     awq_dequantize,
     awq_gemm,
     awq_gemm_num_kranges,
+    awq_gemm_tiled_kranges,
     awq_repack,
     awq_set_exact_weights,
     awq_unpack_nk,

@@ -99,8 +99,10 @@ def awq_unpack_nk(qpacked: torch.Tensor, sz: torch.Tensor, group_size: int, dtyp
 
 def awq_gemm(x: torch.Tensor, qpacked: torch.Tensor, sz: torch.Tensor, group_size: int,
              bias: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """y [M, N] = x [M, K] @ dequant(W) (+ bias) for M <= 64 on a weight re-laid by :func:`awq_repack`; the weight values
-    are exactly awq_dequantize's (awq.py:401-418 computes the same product as dequantize + matmul)."""
+    """y [M, N] = x [M, K] @ dequant(W) (+ bias) for any M on a weight re-laid by :func:`awq_repack` (awq.py:401-418 computes the
+    same product as dequantize + matmul).  M <= 64: the X-stationary kernel (bf16 with one scale group per 128-k block multiplies by
+    the exact (q - z) s unless :func:`awq_set_exact_weights`); M > 64: the tiled kernel, whose weight values are exactly
+    awq_dequantize's for both dtypes.  x may have padded rows (stride a multiple of 8 elements)."""
     _cuda(x, qpacked, sz, bias)
     assert x.dim() == 2 and x.stride(1) == 1 and qpacked.is_contiguous() and sz.is_contiguous()
     m, k = x.shape
@@ -108,13 +110,20 @@ def awq_gemm(x: torch.Tensor, qpacked: torch.Tensor, sz: torch.Tensor, group_siz
     if qpacked.shape[0] * 16 != n or qpacked.shape[1] * 128 != k:
         raise RuntimeError("awq_gemm: x / qpacked / sz shapes do not match")
     out = torch.empty((m, n), dtype=x.dtype, device=x.device)
-    kr = lib.sgl_mi355_awq_gemm_num_kranges(m, k)
+    tiled = m > 64
+    kr = lib.sgl_mi355_awq_gemm_tiled_kranges(m, n, k) if tiled else lib.sgl_mi355_awq_gemm_num_kranges(m, k)
     ws, ws_n = None, 0
     if kr > 1:
         ws, ws_n = _workspace(x.device, kr * m * n)
-    check(lib.sgl_mi355_awq_gemm(ptr(x), x.stride(0), ptr(qpacked), ptr(sz), ptr(out), out.stride(0), ptr(bias), m, n, k,
-                                 int(group_size), dtype_code(x.dtype), ptr(ws), ws_n, current_stream()))
+    fn = lib.sgl_mi355_awq_gemm_tiled if tiled else lib.sgl_mi355_awq_gemm
+    check(fn(ptr(x), x.stride(0), ptr(qpacked), ptr(sz), ptr(out), out.stride(0), ptr(bias), m, n, k, int(group_size),
+             dtype_code(x.dtype), ptr(ws), ws_n, current_stream()))
     return out
+
+
+def awq_gemm_tiled_kranges(m: int, n: int, k: int) -> int:
+    """Split-K ranges of awq_gemm's M > 64 kernel for this shape (1: no slabs)."""
+    return int(lib.sgl_mi355_awq_gemm_tiled_kranges(int(m), int(n), int(k)))
 
 
 def awq_set_exact_weights(on: bool) -> None:

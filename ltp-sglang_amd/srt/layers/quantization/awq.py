@@ -2,10 +2,12 @@
 Marlin / MoE variants are NVIDIA layouts and out of scope).
 
 apply() computes the reference's product (:401-418): ``out = awq_dequantize(qweight, scales, qzeros); y = x @ out (+ bias)``.
-* decode-sized batches (M <= 64): the FUSED int4 dequant-GEMM (``sgl_kernel.awq_gemm``) on a copy of the weight re-laid
-  once in process_weights_after_loading (``awq_repack``; what awq_marlin_repack is to the reference's Marlin path) — only
-  the int4 bytes are read, the weight values are bit-identical to awq_dequantize's;
-* larger M: awq_dequantize (bit-exact HIP kernel) + the tiled MFMA GEMM, the reference's unfused structure."""
+* M <= FUSED_MAX_M: the FUSED int4 dequant-GEMM (``sgl_kernel.awq_gemm``: the X-stationary kernel up to 64 rows, the tiled
+  kernel above) on a copy of the weight re-laid once in process_weights_after_loading (``awq_repack``; what
+  awq_marlin_repack is to the reference's Marlin path) — only the int4 bytes are read, the weight values are bit-identical
+  to awq_dequantize's;
+* larger M, or x in another dtype than the scales: the dense weight (awq_unpack_nk / awq_dequantize, bit-exact HIP kernels)
+  + the tiled MFMA GEMM, the reference's unfused structure."""
 from typing import Any, Dict, List, Optional
 
 import torch
@@ -50,6 +52,12 @@ class AWQConfig(QuantizationConfig):
         return None
 
 
+# Largest M routed to the fused kernel: the largest M of tools/bench_awq.py's sweep at which it beats awq_unpack_nk + dense_linear
+# on all four Qwen2-7B shapes in both dtypes (profiles/awq_tiled_sweep.csv: x1.2 - x2.4 at 128, x1.07 - x2.0 at 256, x1.02 - x1.37 at
+# 512; at 1024 it loses on qkv and o_proj, from 2048 up everywhere: the 128-column tile is bound by the X traffic from L2).
+FUSED_MAX_M = 512
+
+
 class AWQLinearMethod(LinearMethodBase):
     def __init__(self, quant_config: AWQConfig):
         self.quant_config = quant_config
@@ -83,10 +91,10 @@ class AWQLinearMethod(LinearMethodBase):
         out_shape = x.shape[:-1] + (qweight.shape[-1] * self.quant_config.pack_factor,)
         x2d = x.reshape(-1, x.shape[-1])
         packed = getattr(layer, "_awq_packed", None)
-        if packed is not None and x2d.shape[0] <= 64 and x2d.dtype == scales.dtype:
+        if packed is not None and x2d.shape[0] <= FUSED_MAX_M and x2d.dtype == scales.dtype:
             return awq_gemm(x2d.contiguous(), packed[0], packed[1], self.quant_config.group_size, bias).reshape(out_shape)
         if packed is not None and x2d.dtype == scales.dtype:
-            # prefill: the dense [N, K] weight straight from the repacked image (dequantise + transpose in one pass)
+            # large prefill: the dense [N, K] weight straight from the repacked image (dequantise + transpose in one pass)
             w_nk = awq_unpack_nk(packed[0], packed[1], self.quant_config.group_size, scales.dtype)
             return dense_linear(x2d.contiguous(), w_nk, bias).reshape(out_shape)
         w_kn = awq_dequantize(qweight, scales, qzeros)              # [K, N], what the reference multiplies by
