@@ -290,6 +290,19 @@ int sgl_mi355_fp8_gemm_slabs(const void* x, int64_t x_stride_elems, const void* 
 int sgl_mi355_dense_gemm(const void* x, int64_t x_stride_elems, const void* w, int64_t w_stride_elems, void* y,
                          int64_t y_stride_elems, const void* bias, int M, int N, int K, int in_dtype, int out_dtype,
                          float* workspace, int64_t workspace_floats, void* stream);
+/* Block-scaled fp8 GEMM: fp8_blockwise_scaled_mm, sgl-kernel/csrc/gemm/fp8_blockwise_gemm_kernel.cu:345-383 (python
+ * gemm.py:24-31; the block_quant branch of Fp8LinearMethod.apply, python/sglang/srt/layers/quantization/fp8.py:459-478).
+ *   y[m][n] = sum_kb (sum_{k in 128-block kb} x[m][k] w[n][k]) * sx[m][kb] * sw[n / 128][kb] (+ bias[n])
+ * x [M, K] and w [N, K] e4m3fn with row strides in bytes (multiples of 16); y [M, N] bf16 / f16 (out_dtype), row stride in
+ * elements; sx f32 [M, K / 128] and sw f32 [ceil(N / 128), K / 128] with element strides (any layout); bias [N] of out_dtype
+ * or NULL.  K % 128 == 0, N % 16 == 0, any M (0: no launch).  No workspace, allocation or synchronisation. */
+int sgl_mi355_fp8_blockwise_gemm(const void* x, int64_t x_stride_b, const void* w, int64_t w_stride_b, void* y,
+                                 int64_t y_stride, const float* sx, int64_t sx_stride_m, int64_t sx_stride_k, const float* sw,
+                                 int64_t sw_stride_n, int64_t sw_stride_k, const void* bias, int M, int N, int K, int out_dtype,
+                                 void* stream);
+/* Which kernel sgl_mi355_fp8_blockwise_gemm runs (host logic only): 0 = weight-streaming form (M <= 64: 16 weight rows per
+ * workgroup), 1 = 128x128 tile form.  Counterpart of the shape dispatch in fp8_blockwise_gemm_kernel.cu:300-343. */
+int sgl_mi355_fp8_blockwise_gemm_form(int M, int N, int K);
 /* awq_dequantize, sgl-kernel/csrc/gemm/awq_kernel.cu:127-221 (python gemm.py:7-10); HIP reference path
  * awq_dequantize_triton, layers/quantization/awq_triton.py:14-108.  out [K, 8*num_packed_cols] in the scale dtype. */
 int sgl_mi355_awq_dequantize(const void* qweight, const void* scales, const void* qzeros, void* out, int K,

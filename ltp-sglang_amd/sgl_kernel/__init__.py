@@ -48,6 +48,8 @@ from .gemm import (
     awq_unpack_nk,
     dense_linear,
     dense_linear_kranges,
+    fp8_blockwise_gemm_form,
+    fp8_blockwise_scaled_mm,
     fp8_gemm_num_slabs,
     fp8_gemm_slabs,
     fp8_linear_slabs,

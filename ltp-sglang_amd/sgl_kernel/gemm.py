@@ -217,6 +217,73 @@ def fp8_scaled_mm(mat_a, mat_b, scales_a, scales_b, out_dtype, bias=None, out=No
     return out
 
 
+def fp8_blockwise_scaled_mm(mat_a, mat_b, scales_a, scales_b, out_dtype, bias=None):
+    """out[M,N] = sum over 128-wide K blocks kb of (mat_a[M, kb] @ mat_b[kb, N]) * scales_a[m, kb] * scales_b[kb, n // 128] (+ bias[n])
+    (gemm.py:24-31): the block-quantised fp8 linear of DeepSeek-V3 / Qwen3-FP8 style checkpoints.
+
+    mat_a [M, K] row-major, mat_b [K, N] column-major (the ``.T`` of the [N, K] weight), scales_a f32 [M, K / 128], scales_b f32
+    [K / 128, ceil(N / 128)] (the ``.T`` of ``weight_scale_inv``).  Checks and messages follow fp8_blockwise_scaled_mm in
+    sgl-kernel/csrc/gemm/fp8_blockwise_gemm_kernel.cu:351-383, except that the scales may have either layout (row-major as
+    per_token_group_quant_fp8 writes them, or M-major / K-major as the reference wants them): their strides go to the kernel, no
+    copy is made.  N need not be a multiple of 128 (a partial last block has its own scale column).  ``bias`` is not in the
+    reference's signature."""
+    if not mat_a.is_cuda:
+        raise RuntimeError("mat_a must be a CUDA tensor")
+    if not mat_b.is_cuda:
+        raise RuntimeError("mat_b must be a CUDA tensor")
+    if mat_a.dim() != 2:
+        raise RuntimeError("mat_a must be a 2D tensor")
+    if mat_b.dim() != 2:
+        raise RuntimeError("mat_b must be a 2D tensor")
+    if mat_a.stride(1) != 1:
+        raise RuntimeError("mat_a must be a row major tensor")
+    if mat_b.stride(0) != 1:
+        raise RuntimeError("mat_a must be a column major tensor")  # (sic) reference wording
+    if mat_a.size(1) != mat_b.size(0):
+        raise RuntimeError("mat_a and mat_b shapes cannot be multiplied")
+    if (mat_a.size(1) * mat_a.element_size()) % 16 != 0:
+        raise RuntimeError("mat_a must be multiple of 16 bytes for memory alignment")
+    if (mat_b.size(0) * mat_b.element_size()) % 16 != 0:
+        raise RuntimeError("mat_b must be multiple of 16 bytes for memory alignment")
+    if mat_a.dtype != torch.float8_e4m3fn:
+        raise RuntimeError("mat_a must be Float8_e4m3fn")
+    if mat_b.dtype != torch.float8_e4m3fn:
+        raise RuntimeError("mat_b must be Float8_e4m3fn")
+    if out_dtype not in (torch.float16, torch.bfloat16):
+        raise RuntimeError("out_dtype must be Half or BFloat16")
+    m, k = mat_a.shape
+    n = mat_b.size(1)
+    _cuda(scales_a, scales_b, bias)
+    if scales_a.dim() != 2 or scales_a.size(0) != m or scales_a.size(1) != k // 128:
+        raise RuntimeError("size of scales_a is not matched")
+    if scales_b.dim() != 2 or scales_b.size(0) != k // 128 or scales_b.size(1) != (n + 127) // 128:
+        raise RuntimeError("size of scales_b is not matched")
+    if scales_a.dtype != torch.float32:
+        raise RuntimeError("scales_a must be Float32")
+    if scales_b.dtype != torch.float32:
+        raise RuntimeError("scales_b must be Float32")
+    if bias is not None:
+        if bias.numel() != n:
+            raise RuntimeError("size of bias is not matched")
+        if not bias.is_contiguous():
+            raise RuntimeError("bias must be contiguous")
+        if bias.dtype != out_dtype:
+            raise RuntimeError("bias dtype must match output dtype")
+    out = torch.empty((m, n), dtype=out_dtype, device=mat_a.device)
+    if (out.size(1) * out.element_size()) % 16 != 0:
+        raise RuntimeError("out must be multiple of 16 bytes for memory alignment")
+    check(lib.sgl_mi355_fp8_blockwise_gemm(ptr(mat_a), mat_a.stride(0), ptr(mat_b), mat_b.stride(1), ptr(out), out.stride(0),
+                                           ptr(scales_a), scales_a.stride(0), scales_a.stride(1),
+                                           ptr(scales_b), scales_b.stride(1), scales_b.stride(0), ptr(bias), m, n, k,
+                                           dtype_code(out_dtype), current_stream()))
+    return out
+
+
+def fp8_blockwise_gemm_form(m: int, n: int, k: int) -> int:
+    """Which kernel fp8_blockwise_scaled_mm runs for this shape: 0 = weight-streaming form (M <= 64), 1 = 128x128 tile form."""
+    return int(lib.sgl_mi355_fp8_blockwise_gemm_form(int(m), int(n), int(k)))
+
+
 def fp8_linear_slabs(x_q: torch.Tensor, weight_nk: torch.Tensor, m: int, n: int, k: int, out: Optional[torch.Tensor] = None,
                      min_kranges: int = 1) -> torch.Tensor:
     """Raw f32 split-K partial sums [S, M, N] of x_q[M,K] @ weight_nk[N,K]^T (no scales): the producer half of the
