@@ -303,6 +303,24 @@ int sgl_mi355_fp8_blockwise_gemm(const void* x, int64_t x_stride_b, const void* 
 /* Which kernel sgl_mi355_fp8_blockwise_gemm runs (host logic only): 0 = weight-streaming form (M <= 64: 16 weight rows per
  * workgroup), 1 = 128x128 tile form.  Counterpart of the shape dispatch in fp8_blockwise_gemm_kernel.cu:300-343. */
 int sgl_mi355_fp8_blockwise_gemm_form(int M, int N, int K);
+/* int8 w8a8 GEMM: int8_scaled_mm, sgl-kernel/csrc/gemm/int8_gemm_kernel.cu:663-730 (schema common_extension.cc:102; python
+ * gemm.py int8_scaled_mm; W8A8Int8LinearMethod.apply, python/sglang/srt/layers/quantization/w8a8_int8.py:366-386).
+ *   y[m][n] = float(sum_k x[m][k] w[n][k]) * scales_a[m] * scales_b[n] (+ bias[n])
+ * x [M, K] and w [N, K] int8 with row strides in bytes (multiples of 16); y [M, N] bf16 / f16 (out_dtype), row stride in elements;
+ * scales f32; bias [N] of out_dtype or NULL.  K % 64 == 0, K < 131072, N % 16 == 0, any M (0: no launch).  int32 accumulation
+ * (exact), one epilogue for every path.  workspace: optional scratch for the tile form's split-K at 64 < M <= 512 (int32 partial
+ * sums stored in it; its last 512 words are left alone; NULL: no split-K).  No allocation or synchronisation. */
+int sgl_mi355_int8_gemm(const void* x, int64_t x_stride_b, const void* w, int64_t w_stride_b, void* y, int64_t y_stride,
+                        const float* scales_a, const float* scales_b, const void* bias, int M, int N, int K, int out_dtype,
+                        float* workspace, int64_t workspace_floats, void* stream);
+/* Which kernel sgl_mi355_int8_gemm runs (host logic only): 0 = weight-streaming form (M <= 64), 1 = 128x128 tile form.
+ * Counterpart of the shape dispatch in int8_gemm_kernel.cu:216-330,560-660. */
+int sgl_mi355_int8_gemm_form(int M, int N, int K);
+/* per_token_quant_int8, python/sglang/srt/layers/quantization/int8_kernel.py (called at w8a8_int8.py:382): per row in f32,
+ * absmax = max(max |x|, 1e-10), s = absmax / 127, q = round_half_away_from_zero(x * (127 / absmax)).  x [M, K] bf16 / f16, row
+ * stride in elements (a multiple of 8); q int8 [M, K]; s f32 [M]. */
+int sgl_mi355_per_token_quant_int8(const void* x, int64_t x_stride, void* q, float* s, int64_t M, int64_t K, int dtype,
+                                   void* stream);
 /* awq_dequantize, sgl-kernel/csrc/gemm/awq_kernel.cu:127-221 (python gemm.py:7-10); HIP reference path
  * awq_dequantize_triton, layers/quantization/awq_triton.py:14-108.  out [K, 8*num_packed_cols] in the scale dtype. */
 int sgl_mi355_awq_dequantize(const void* qweight, const void* scales, const void* qzeros, void* out, int K,

@@ -7,6 +7,8 @@
 //       (dynamic) scale = atomicMax(absmax / 448) ; q = sat(x * (1 / scale))
 //   sgl_per_token_group_quant_fp8  sgl-kernel/csrc/gemm/per_token_group_quant_8bit.cu
 //       y_s = max(absmax, eps) / fp8_max ; q = clamp(x / y_s, fp8_min, fp8_max)
+//   per_token_quant_int8      python/sglang/srt/layers/quantization/int8_kernel.py (w8a8_int8.py:382) -- the per-token kernels below
+//       with the int8 policy: scale = max(absmax, 1e-10) / 127 ; q = round_half_away(x * (127 / max(absmax, 1e-10)))
 // Divisions are IEEE (this file is built without fast-math); conversion is the hardware
 // v_cvt_pk_fp8_f32 (RNE) after an explicit clamp to +-448.
 //
@@ -49,8 +51,33 @@ __device__ __forceinline__ uint8_t cvt1_fp8(float f) {
   return (uint8_t)(__builtin_amdgcn_cvt_pk_fp8_f32(f, 0.f, 0, false) & 0xff);
 }
 
+// What a per-token kernel does with a row's absmax: the scale it reports, the factor it multiplies by, and the 8-byte pack.
+struct Fp8Quant {   // sgl_per_token_quant_fp8
+  static __device__ __forceinline__ float scale(float amax) { return amax / kFp8Max; }
+  static __device__ __forceinline__ float factor(float amax, float scale) { return (scale == 0.f) ? 0.f : 1.0f / scale; }
+  static __device__ __forceinline__ u32x2_t pack(const float (&v)[8], float fac) {
+    float f[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) f[j] = clamp448(v[j] * fac);
+    return pack8_fp8(f);
+  }
+};
+// per_token_quant_int8 (python/sglang/srt/layers/quantization/int8_kernel.py, used by w8a8_int8.py:382): absmax = max(max |x|, 1e-10),
+// scale = absmax / 127, q = round_half_away_from_zero(x * (127 / absmax)); |x * (127 / absmax)| <= 127 (1 + 2^-23) rounds to at
+// most 127, so -128 never appears and no clamp is needed
+struct Int8Quant {
+  static __device__ __forceinline__ float scale(float amax) { return fmaxf(amax, 1e-10f) / 127.0f; }
+  static __device__ __forceinline__ float factor(float amax, float) { return 127.0f / fmaxf(amax, 1e-10f); }
+  static __device__ __forceinline__ u32x2_t pack(const float (&v)[8], float fac) {
+    uint32_t d[2] = {0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) d[j >> 2] |= ((uint32_t)(int)roundf(v[j] * fac) & 0xFFu) << (8 * (j & 3));
+    return u32x2_t{d[0], d[1]};
+  }
+};
+
 // One workgroup of NT threads per token when TOK_PER_WG == 1, else one wave per token.
-template <typename T, int NT, int TOK_PER_WG>
+template <typename T, int NT, int TOK_PER_WG, typename Q>
 __global__ __launch_bounds__(NT) void per_token_quant_kernel(const T* __restrict__ in, uint8_t* __restrict__ out_q,
                                                              float* __restrict__ out_s, int64_t hidden, int64_t tokens,
                                                              int64_t in_stride) {
@@ -80,16 +107,14 @@ __global__ __launch_bounds__(NT) void per_token_quant_kernel(const T* __restrict
     for (int i = 1; i < NT / 64; ++i) amax = fmaxf(amax, red[i]);
   }
   if (!live) return;
-  const float scale = amax / kFp8Max;
+  const float scale = Q::scale(amax);
   if (t == 0) out_s[token] = scale;
-  const float inv = (scale == 0.f) ? 0.f : 1.0f / scale;
+  const float inv = Q::factor(amax, scale);
   uint8_t* orow = out_q + token * hidden;
   for (int64_t i = t; i < nvec; i += TPT) {
     float f[8];
     load8(row + i * 8, f);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) f[j] = clamp448(f[j] * inv);
-    *(u32x2_t*)(orow + i * 8) = pack8_fp8(f);
+    *(u32x2_t*)(orow + i * 8) = Q::pack(f, inv);
   }
 }
 
@@ -214,7 +239,7 @@ __global__ __launch_bounds__(256) void per_token_group_quant_kernel(const T* __r
 // hidden = 14336, twice), which is all a kernel with 32 workgroups is made of.  Same arithmetic, bit for bit.
 // NT: prefill-sized launches (the row is read once, the codes are read once by a GEMM that streams gigabytes): non-temporal loads and
 // stores, so the stream does not evict what the neighbouring kernels re-read
-template <typename T, int MAXV, bool NT = false>
+template <typename T, int MAXV, bool NT, typename Q>
 __global__ __launch_bounds__(256) void per_token_quant_row_kernel(const T* __restrict__ in, uint8_t* __restrict__ out_q,
                                                                   float* __restrict__ out_s, int hidden, int64_t in_stride) {
   __shared__ float red[4];
@@ -246,24 +271,21 @@ __global__ __launch_bounds__(256) void per_token_quant_row_kernel(const T* __res
   if ((tid & 63) == 0) red[tid >> 6] = amax;
   __syncthreads();
   amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  const float scale = amax / kFp8Max;
+  const float scale = Q::scale(amax);
   if (tid == 0) out_s[token] = scale;
-  const float inv = (scale == 0.f) ? 0.f : 1.0f / scale;
+  const float inv = Q::factor(amax, scale);
   uint8_t* orow = out_q + token * hidden;
 #pragma unroll
   for (int it = 0; it < MAXV; ++it) {
     const int i = tid + it * 256;
     if (i < nvec) {
-      float f[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) f[j] = clamp448(vals[it][j] * inv);
-      if constexpr (NT) __builtin_nontemporal_store(pack8_fp8(f), (u32x2_t*)(orow + i * 8));
-      else *(u32x2_t*)(orow + i * 8) = pack8_fp8(f);
+      if constexpr (NT) __builtin_nontemporal_store(Q::pack(vals[it], inv), (u32x2_t*)(orow + i * 8));
+      else *(u32x2_t*)(orow + i * 8) = Q::pack(vals[it], inv);
     }
   }
 }
 
-template <typename T>
+template <typename T, typename Q>
 int launch_per_token(const void* in, void* q, float* s, int64_t tokens, int64_t hidden, int64_t in_stride, hipStream_t st) {
 #ifndef SGL_QUANT_ROW_WIDE
 #define SGL_QUANT_ROW_WIDE 1
@@ -279,9 +301,9 @@ int launch_per_token(const void* in, void* q, float* s, int64_t tokens, int64_t 
     const bool nt = SGL_ROW_NT && tokens * hidden >= (1ll << 27);
 #define SGL_ROWQ(MV)                                                                                                             \
   do {                                                                                                                           \
-    if (nt) hipLaunchKernelGGL((per_token_quant_row_kernel<T, MV, true>), dim3((unsigned)tokens), dim3(256), 0, st, (const T*)in, \
+    if (nt) hipLaunchKernelGGL((per_token_quant_row_kernel<T, MV, true, Q>), dim3((unsigned)tokens), dim3(256), 0, st, (const T*)in, \
                                (uint8_t*)q, s, (int)hidden, in_stride);                                                          \
-    else hipLaunchKernelGGL((per_token_quant_row_kernel<T, MV, false>), dim3((unsigned)tokens), dim3(256), 0, st, (const T*)in,   \
+    else hipLaunchKernelGGL((per_token_quant_row_kernel<T, MV, false, Q>), dim3((unsigned)tokens), dim3(256), 0, st, (const T*)in,   \
                             (uint8_t*)q, s, (int)hidden, in_stride);                                                             \
   } while (0)
     if (hidden <= 256 * 8 * 2) SGL_ROWQ(2);
@@ -292,10 +314,10 @@ int launch_per_token(const void* in, void* q, float* s, int64_t tokens, int64_t 
     return SGL_MI355_OK;
   }
   if (tokens >= 2048) {
-    hipLaunchKernelGGL((per_token_quant_kernel<T, 256, 4>), dim3((unsigned)((tokens + 3) / 4)), dim3(256), 0, st,
+    hipLaunchKernelGGL((per_token_quant_kernel<T, 256, 4, Q>), dim3((unsigned)((tokens + 3) / 4)), dim3(256), 0, st,
                        (const T*)in, (uint8_t*)q, s, hidden, tokens, in_stride);
   } else {
-    hipLaunchKernelGGL((per_token_quant_kernel<T, 256, 1>), dim3((unsigned)tokens), dim3(256), 0, st, (const T*)in,
+    hipLaunchKernelGGL((per_token_quant_kernel<T, 256, 1, Q>), dim3((unsigned)tokens), dim3(256), 0, st, (const T*)in,
                        (uint8_t*)q, s, hidden, tokens, in_stride);
   }
   SGL_HIP_LAUNCH_CHECK();
@@ -315,8 +337,24 @@ extern "C" int sgl_mi355_per_token_quant_fp8(const void* input, int64_t input_st
             "per_token_quant_fp8: rows must be 16-byte aligned");
   SGL_CHECK(in_dtype == SGL_BF16 || in_dtype == SGL_F16, "per_token_quant_fp8: input must be bf16 or f16");
   hipStream_t st = (hipStream_t)stream;
-  return in_dtype == SGL_BF16 ? launch_per_token<__bf16>(input, output_q, output_s, num_tokens, hidden_dim, input_stride, st)
-                              : launch_per_token<_Float16>(input, output_q, output_s, num_tokens, hidden_dim, input_stride, st);
+  return in_dtype == SGL_BF16 ? launch_per_token<__bf16, Fp8Quant>(input, output_q, output_s, num_tokens, hidden_dim, input_stride, st)
+                              : launch_per_token<_Float16, Fp8Quant>(input, output_q, output_s, num_tokens, hidden_dim, input_stride, st);
+}
+
+// per_token_quant_int8 (python/sglang/srt/layers/quantization/int8_kernel.py; W8A8Int8LinearMethod.apply, w8a8_int8.py:382): the same
+// kernels and launch shapes with the int8 policy.  x [M, K] bf16 / f16 with a row stride in elements, q int8 [M, K], s f32 [M, 1].
+extern "C" int sgl_mi355_per_token_quant_int8(const void* x, int64_t x_stride, void* q, float* s, int64_t M, int64_t K, int dtype,
+                                              void* stream) {
+  SGL_CHECK(M >= 0 && K >= 0, "per_token_quant_int8: negative shape");
+  if (M == 0 || K == 0) return SGL_MI355_OK;
+  SGL_CHECK(x && q && s, "per_token_quant_int8: null pointer");
+  SGL_CHECK(K % 8 == 0, "per_token_quant_int8: K=%lld must be a multiple of 8", (long long)K);
+  SGL_CHECK(x_stride >= K && x_stride % 8 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)q % 8) == 0,
+            "per_token_quant_int8: rows must be 16-byte aligned");
+  SGL_CHECK(dtype == SGL_BF16 || dtype == SGL_F16, "per_token_quant_int8: input must be bf16 or f16");
+  hipStream_t st = (hipStream_t)stream;
+  return dtype == SGL_BF16 ? launch_per_token<__bf16, Int8Quant>(x, q, s, M, K, x_stride, st)
+                           : launch_per_token<_Float16, Int8Quant>(x, q, s, M, K, x_stride, st);
 }
 
 extern "C" int sgl_mi355_per_tensor_quant_fp8(const void* input, void* output_q, float* output_s, int64_t num_elements,

@@ -54,9 +54,12 @@ from .gemm import (
     fp8_gemm_slabs,
     fp8_linear_slabs,
     fp8_scaled_mm,
+    int8_gemm_form,
+    int8_scaled_mm,
     sgl_per_tensor_quant_fp8,
     sgl_per_token_group_quant_fp8,
     sgl_per_token_quant_fp8,
+    sgl_per_token_quant_int8,
 )
 from .kvcache import (
     compute_position,

@@ -284,6 +284,80 @@ def fp8_blockwise_gemm_form(m: int, n: int, k: int) -> int:
     return int(lib.sgl_mi355_fp8_blockwise_gemm_form(int(m), int(n), int(k)))
 
 
+def int8_scaled_mm(mat_a, mat_b, scales_a, scales_b, out_dtype, bias=None):
+    """out[M,N] = float(mat_a[M,K] @ mat_b[K,N] in int32) * scales_a[m] * scales_b[n] (+ bias[n]) (gemm.py:13-22): the w8a8 int8
+    linear.  mat_a int8 [M, K] row-major (rows may be padded by a multiple of 16 bytes), mat_b int8 [K, N] column-major (the
+    ``.t()`` of the [N, K] weight).  Checks and messages follow int8_scaled_mm in sgl-kernel/csrc/gemm/int8_gemm_kernel.cu:670-694;
+    this build's narrower domain (K % 64, N % 16, K < 131072, 16-byte aligned rows) raises the C library's own messages."""
+    if not mat_a.is_cuda:
+        raise RuntimeError("mat_a must be a CUDA tensor")
+    if not mat_b.is_cuda:
+        raise RuntimeError("mat_b must be a CUDA tensor")
+    if mat_a.dim() != 2:
+        raise RuntimeError("mat_a must be a 2D tensor")
+    if mat_b.dim() != 2:
+        raise RuntimeError("mat_b must be a 2D tensor")
+    if mat_a.stride(1) != 1:
+        raise RuntimeError("mat_a must be a row major tensor")
+    if mat_b.stride(0) != 1:
+        raise RuntimeError("mat_a must be a column major tensor")  # (sic) reference wording
+    if mat_a.size(1) != mat_b.size(0):
+        raise RuntimeError("mat_a and mat_b shapes cannot be multiplied")
+    if mat_a.size(1) % 16 != 0:
+        raise RuntimeError("mat_a.size(1) must be multiple of 16 for memory alignment")
+    if mat_b.size(0) % 16 != 0:
+        raise RuntimeError("mat_b.size(0) must be multiple of 16 for memory alignment")
+    if mat_b.size(1) % 8 != 0:
+        raise RuntimeError("mat_b.size(1) must be multiple of 8 for memory alignment")
+    if mat_a.dtype != torch.int8:
+        raise RuntimeError("mat_a must be Int8")
+    if mat_b.dtype != torch.int8:
+        raise RuntimeError("mat_b must be Int8")
+    if out_dtype not in (torch.float16, torch.bfloat16):
+        raise RuntimeError("out_dtype must be Half or BFloat16")
+    if scales_a.numel() != mat_a.size(0):
+        raise RuntimeError("size of scales_a is not matched")
+    if scales_b.numel() != mat_b.size(1):
+        raise RuntimeError("size of scales_b is not matched")
+    if not scales_a.is_contiguous():
+        raise RuntimeError("scales_a must be contiguous")
+    if not scales_b.is_contiguous():
+        raise RuntimeError("scales_b msut be contiguous")
+    if scales_a.dtype != torch.float32:
+        raise RuntimeError("scales_a must be Float32")
+    if scales_b.dtype != torch.float32:
+        raise RuntimeError("scales_b must be Float32")
+    if bias is not None:
+        if bias.numel() != mat_b.size(1):
+            raise RuntimeError("size of bias is not matched")
+        if not bias.is_contiguous():
+            raise RuntimeError("bias must be contiguous")
+        if bias.dtype != out_dtype:
+            raise RuntimeError("bias dtype must match output dtype")
+    _cuda(scales_a, scales_b, bias)
+    m, k = mat_a.shape
+    n = mat_b.size(1)
+    out = torch.empty((m, n), dtype=out_dtype, device=mat_a.device)
+    ws, ws_n = _tiled_workspace(mat_a.device) if 64 < m <= 512 else (None, 0)   # the tile form's split-K band
+    check(lib.sgl_mi355_int8_gemm(ptr(mat_a), mat_a.stride(0), ptr(mat_b), mat_b.stride(1), ptr(out), out.stride(0), ptr(scales_a),
+                                  ptr(scales_b), ptr(bias), m, n, k, dtype_code(out_dtype), ptr(ws), ws_n, current_stream()))
+    return out
+
+
+def int8_gemm_form(m: int, n: int, k: int) -> int:
+    """Which kernel int8_scaled_mm runs for this shape: 0 = weight-streaming form (M <= 64), 1 = 128x128 tile form."""
+    return int(lib.sgl_mi355_int8_gemm_form(int(m), int(n), int(k)))
+
+
+def sgl_per_token_quant_int8(input: torch.Tensor, output_q: torch.Tensor, output_s: torch.Tensor) -> None:
+    """per_token_quant_int8's kernel (int8_kernel.py); in-place outputs: output_q int8 [M, K], output_s f32 [M] or [M, 1]."""
+    _cuda(input, output_q, output_s)
+    assert input.dim() == 2 and input.stride(1) == 1 and output_q.is_contiguous() and output_s.is_contiguous()
+    assert output_q.dtype == torch.int8 and output_s.dtype == torch.float32
+    check(lib.sgl_mi355_per_token_quant_int8(ptr(input), input.stride(0), ptr(output_q), ptr(output_s), input.shape[0],
+                                             input.shape[1], dtype_code(input.dtype), current_stream()))
+
+
 def fp8_linear_slabs(x_q: torch.Tensor, weight_nk: torch.Tensor, m: int, n: int, k: int, out: Optional[torch.Tensor] = None,
                      min_kranges: int = 1) -> torch.Tensor:
     """Raw f32 split-K partial sums [S, M, N] of x_q[M,K] @ weight_nk[N,K]^T (no scales): the producer half of the

@@ -2,7 +2,7 @@
 reference's own Python wrappers -- which call ``torch.ops.sgl_kernel.<op>.default(...)``
 (sgl-kernel/python/sgl_kernel/gemm.py:34-42,100-146, elementwise.py, attention.py:12-52) -- resolve to the C-ABI kernels.
 
-Schemas are the reference's ``m.def`` strings (sgl-kernel/csrc/common_extension.cc:56-59,69-82,98-130 (fp8_blockwise_scaled_mm: :112) and, for the two native
+Schemas are the reference's ``m.def`` strings (sgl-kernel/csrc/common_extension.cc:56-59,69-82,98-130 (int8_scaled_mm: :102, fp8_blockwise_scaled_mm: :112) and, for the two native
 attention ops, csrc/cpu/torch_extension_cpu.cpp:264-275); kernels are registered for the CUDA dispatch key, which is the key
 HIP tensors dispatch on (torch_extension_rocm.cc:21-27).  Importing ``ltp_sglang_amd.sgl_kernel`` runs register() once; if a
 library that already defines an op is loaded in the same process the definition is left alone and only this build's kernel
@@ -16,6 +16,7 @@ from . import gemm as _gemm
 
 _SCHEMAS = {
     "fp8_scaled_mm": "(Tensor mat_a, Tensor mat_b, Tensor scales_a, Tensor scales_b, ScalarType out_dtype, Tensor? bias) -> Tensor",
+    "int8_scaled_mm": "(Tensor mat_a, Tensor mat_b, Tensor scales_a, Tensor scales_b, ScalarType out_dtype, Tensor? bias) -> Tensor",
     "fp8_blockwise_scaled_mm": "(Tensor mat_a, Tensor mat_b, Tensor scales_a, Tensor scales_b, ScalarType out_dtype) -> Tensor",
     "sgl_per_token_group_quant_fp8": "(Tensor input, Tensor output_q, Tensor output_s, int group_size, float eps, float fp8_min, float fp8_max, bool scale_ue8m0) -> ()",
     "sgl_per_tensor_quant_fp8": "(Tensor input, Tensor output_q, Tensor output_s, bool is_static) -> ()",
@@ -57,6 +58,7 @@ def _fp8_blockwise_scaled_mm(mat_a, mat_b, scales_a, scales_b, out_dtype):
 
 _IMPLS = {
     "fp8_scaled_mm": _gemm.fp8_scaled_mm,
+    "int8_scaled_mm": _gemm.int8_scaled_mm,
     "fp8_blockwise_scaled_mm": _fp8_blockwise_scaled_mm,
     "sgl_per_token_group_quant_fp8": _gemm.sgl_per_token_group_quant_fp8,
     "sgl_per_tensor_quant_fp8": _gemm.sgl_per_tensor_quant_fp8,

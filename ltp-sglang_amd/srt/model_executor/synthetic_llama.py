@@ -23,6 +23,7 @@ from ..layers.layernorm import RMSNorm
 from ..layers.linear import MergedColumnParallelLinear, QKVParallelLinear, RowParallelLinear
 from ..layers.quantization import get_quantization_config
 from ..layers.quantization.w8a8_fp8 import per_channel_quant_fp8
+from ..layers.quantization.w8a8_int8 import per_channel_quant_int8
 from ..layers.radix_attention import RadixAttention
 from ..layers.rotary_embedding import get_rope
 from ..mem_cache.allocator import TokenToKVPoolAllocator
@@ -187,12 +188,18 @@ class LlamaForCausalLM(nn.Module):
     @torch.no_grad()
     def init_random_weights(self, seed: int = 0, std: float = 0.02):
         """bf16 N(0, std) weights, then each linear's own process_weights_after_loading (fp8 per-channel quantiser:
-        w8a8_fp8.py:119-126; AWQ: random int32 packs + U(0,1)*0.01 scales as test_awq_dequant.py:71-100)."""
+        w8a8_fp8.py:119-126; w8a8_int8: the drawn matrix quantised per channel into weight / weight_scale; AWQ: random int32 packs + U(0,1)*0.01 scales as test_awq_dequant.py:71-100)."""
         dev = self.embed_tokens.device
         g = torch.Generator(device=dev).manual_seed(seed)
 
         def randn(shape, s=std):
             return (torch.randn(shape, generator=g, device=dev, dtype=torch.float32) * s).to(self.dtype)
+
+        def set_weight(mod, w):
+            if mod.weight.dtype == torch.int8:   # w8a8_int8: the checkpoint holds int8 rows and their scales
+                w, scale = per_channel_quant_int8(w)
+                mod.weight_scale.copy_(scale)
+            mod.weight.copy_(w)
 
         self.embed_tokens.copy_(randn(self.embed_tokens.shape, 1.0))
         vs = self.cfg.vocab_size // self.tp_size
@@ -208,10 +215,10 @@ class LlamaForCausalLM(nn.Module):
                 mod.qzeros.copy_(torch.randint(0, 2**31 - 1, mod.qzeros.shape, generator=g, device=dev, dtype=torch.int32))
                 mod.scales.copy_((torch.rand(mod.scales.shape, generator=g, device=dev) * 0.01 * 0.3).to(self.dtype))
             elif hasattr(mod, "shard_cols"):  # row parallel: every rank draws the full matrix and keeps its K slice
-                mod.weight.copy_(mod.shard_cols(randn((mod.output_size, mod.input_size))))
+                set_weight(mod, mod.shard_cols(randn((mod.output_size, mod.input_size))))
             else:                             # column parallel (incl. merged / qkv): keep this rank's rows
                 full_rows = (mod.total_num_heads + 2 * mod.total_num_kv_heads) * mod.head_size if hasattr(mod, "total_num_heads") else mod.output_size
-                mod.weight.copy_(mod.shard_rows(randn((full_rows, mod.input_size))))
+                set_weight(mod, mod.shard_rows(randn((full_rows, mod.input_size))))
             if getattr(mod, "bias", None) is not None:
                 if hasattr(mod, "shard_rows"):
                     full_rows = (mod.total_num_heads + 2 * mod.total_num_kv_heads) * mod.head_size if hasattr(mod, "total_num_heads") else mod.output_size
