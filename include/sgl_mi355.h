@@ -504,6 +504,41 @@ int sgl_mi355_awq_qkv_rope_set_kv(const void* x, int64_t x_stride_elems, const v
                                   int num_kv_heads, int head_dim, int K, int group_size, int dtype, int kv_dtype, float k_scale,
                                   float v_scale, void* stream);
 
+/* ---- NVFP4 (w4a16) linear: ModelOpt NVFP4 checkpoints through petit_nvfp4 -----------------------
+ * PetitNvFp4LinearMethod (python/sglang/srt/layers/quantization/petit.py:134-252) -> apply_petit_nvfp4_linear
+ * (petit_utils.py:78-104) -> mul_nvfp4_a16 of the petit_kernel wheel, which the reference does not contain: these kernels are
+ * written from the format.  weight uint8 [N, K/2] (element 2j in the low nibble of byte j, 2j + 1 in the high one; a nibble =
+ * sign bit + index into {0, .5, 1, 1.5, 2, 3, 4, 6}), weight_scale float8_e4m3fn [N, K/16], weight_scale_2 one f32:
+ *   W[n][k] = e2m1(nibble(n, k)) * float(weight_scale[n][k / 16])      (exact in bf16 and f16; the kernels' operand bit for bit)
+ *   y[m][n] = T( f32(sum_k x[m][k] W[n][k]) * weight_scale_2 (+ bias[n]) )      one rounding (the reference adds the bias to the
+ *                                                                              rounded output, petit_utils.py:101-102)
+ * One-off load-time re-layout into MFMA-fragment order (the role of repack_nvfp4 / process_nvfp4_scales, petit_utils.py:61-75):
+ *   qpacked uint32 [N/16][K/128][64 lanes][4]: word s of lane (a = n % 16, g) = W[n][128 b + 32 s + 8 g + e], e = 0..7, nibble e
+ *           at bits 4 e (the checkpoint's own four bytes);
+ *   spacked uint32 [N/16][K/128][32]: word (g / 2) * 16 + a, byte s = weight_scale[n][8 b + 2 s + g / 2]: the four scale bytes of
+ *           lane (a, g), one coalesced 4-byte load per lane and block; 9/16 byte per weight in all.
+ * K % 128 == 0, N % 16 == 0; scale bytes 0x7F / 0xFF (NaN) are outside the contract. */
+int sgl_mi355_nvfp4_repack(const void* weight, const void* weight_scale, void* qpacked, void* spacked, int N, int K,
+                           void* stream);
+/* apply_petit_nvfp4_linear (petit_utils.py:78-104): y = x . W^T * *global_scale (+ bias) on the repacked image, x / y / bias
+ * bf16 or f16 (dtype), f32 accumulation.  global_scale is a DEVICE pointer to weight_scale_2 (petit.py:226-236), never read on
+ * the host.  Any M (0: no launch), x rows may be padded (stride a multiple of 8 elements).  workspace: kranges x M x N floats
+ * when sgl_mi355_nvfp4_gemm_kranges(M, N, K) > 1.  Asynchronous on stream, allocation- and sync-free. */
+int sgl_mi355_nvfp4_gemm(const void* x, int64_t x_stride_elems, const void* qpacked, const void* spacked, void* y,
+                         int64_t y_stride_elems, const float* global_scale, const void* bias, int M, int N, int K, int dtype,
+                         float* workspace, int64_t workspace_floats, void* stream);
+/* Which kernel sgl_mi355_nvfp4_gemm runs (host logic only; mul_nvfp4_a16's solution_id, petit_utils.py:90-100, is the
+ * reference's counterpart): 0 = weight-streaming form (M <= 64), 1 = 128x128 tile form. */
+int sgl_mi355_nvfp4_gemm_form(int M, int N, int K);
+/* split-K ranges of sgl_mi355_nvfp4_gemm (petit_utils.py:90-100 leaves the split to the wheel): form 0: 4096 k per range for
+ * M <= 32, 2048 k for 33..64 rows; form 1: whole 128-k blocks, at least three per range; 1: no workspace */
+int sgl_mi355_nvfp4_gemm_kranges(int M, int N, int K);
+/* Dense W [N, K] (row-major, bf16 / f16) from the checkpoint tensors (petit.py:187-224); any K % 16 == 0: serves large M and the
+ * shapes the fused kernel does not take.  global_scale null: WITHOUT weight_scale_2, bit-exact; else a device pointer to it and
+ * out = T(W * weight_scale_2), one rounding of the exact product. */
+int sgl_mi355_nvfp4_dequantize(const void* weight, const void* weight_scale, const float* global_scale, void* out, int N, int K,
+                               int dtype, void* stream);
+
 /* out[cols, rows] = in[rows, cols]^T for 16-bit elements (weight re-layout between awq_dequantize's [K, N] and
  * the [N, K] the GEMMs stream; AWQLinearMethod.apply, layers/quantization/awq.py:401-418) */
 int sgl_mi355_transpose_2d(void* out, const void* in, int rows, int cols, void* stream);

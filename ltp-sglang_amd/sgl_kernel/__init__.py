@@ -56,6 +56,11 @@ from .gemm import (
     fp8_scaled_mm,
     int8_gemm_form,
     int8_scaled_mm,
+    nvfp4_dequantize,
+    nvfp4_gemm,
+    nvfp4_gemm_form,
+    nvfp4_gemm_kranges,
+    nvfp4_repack,
     sgl_per_tensor_quant_fp8,
     sgl_per_token_group_quant_fp8,
     sgl_per_token_quant_fp8,

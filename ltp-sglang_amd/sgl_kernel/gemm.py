@@ -142,6 +142,80 @@ def awq_gemm_num_kranges(m: int, k: int) -> int:
     return int(lib.sgl_mi355_awq_gemm_num_kranges(int(m), int(k)))
 
 
+def _nvfp4_checkpoint(who: str, weight: torch.Tensor, weight_scale: torch.Tensor) -> Tuple[int, int]:
+    """(N, K) of a ModelOpt NVFP4 checkpoint pair: weight uint8 [N, K/2], weight_scale float8_e4m3fn [N, K/16] (petit.py:187-224)."""
+    _cuda(weight, weight_scale)
+    if weight.dtype != torch.uint8 or weight_scale.dtype != torch.float8_e4m3fn:
+        raise RuntimeError(f"{who}: weight must be uint8 and weight_scale float8_e4m3fn")
+    if weight.dim() != 2 or weight_scale.dim() != 2 or not weight.is_contiguous() or not weight_scale.is_contiguous():
+        raise RuntimeError(f"{who}: weight and weight_scale must be contiguous 2-D tensors")
+    n, k = weight.shape[0], weight.shape[1] * 2
+    if k % 16 != 0 or tuple(weight_scale.shape) != (n, k // 16):
+        raise RuntimeError(f"{who}: weight [N, K/2] and weight_scale [N, K/16] shapes do not match")
+    return n, k
+
+
+def nvfp4_repack(weight: torch.Tensor, weight_scale: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One-off re-layout of an NVFP4 checkpoint weight into MFMA-fragment order for :func:`nvfp4_gemm` (the role of repack_nvfp4 /
+    process_nvfp4_scales, petit_utils.py:61-75).  Returns (qpacked int32 [N/16, K/128, 64, 4], spacked int32 [N/16, K/128, 32]);
+    layouts in include/sgl_mi355.h.  K % 128 == 0, N % 16 == 0."""
+    n, k = _nvfp4_checkpoint("nvfp4_repack", weight, weight_scale)
+    if k % 128 != 0 or n % 16 != 0:
+        raise RuntimeError(f"nvfp4_repack: needs K % 128 == 0 and N % 16 == 0 (K={k} N={n})")
+    qpacked = torch.empty((n // 16, k // 128, 64, 4), dtype=torch.int32, device=weight.device)
+    spacked = torch.empty((n // 16, k // 128, 32), dtype=torch.int32, device=weight.device)
+    check(lib.sgl_mi355_nvfp4_repack(ptr(weight), ptr(weight_scale), ptr(qpacked), ptr(spacked), n, k, current_stream()))
+    return qpacked, spacked
+
+
+def nvfp4_gemm(x: torch.Tensor, qpacked: torch.Tensor, spacked: torch.Tensor, global_scale: torch.Tensor,
+               bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y [M, N] = T(f32(x [M, K] @ W^T) * global_scale (+ bias)) on a weight re-laid by :func:`nvfp4_repack`: mul_nvfp4_a16 + the
+    bias of apply_petit_nvfp4_linear (petit_utils.py:78-104), rounded once.  W[n][k] = e2m1 nibble * e4m3 group scale, exact in the
+    MFMA operand.  global_scale: the f32 device scalar weight_scale_2 (read by the kernel, never on the host).  x bf16 / f16, rows
+    may be padded (stride a multiple of 8 elements); any M: the weight-streaming kernel up to 64 rows, the tile kernel above."""
+    _cuda(x, qpacked, spacked, global_scale, bias)
+    assert x.dim() == 2 and x.stride(1) == 1 and qpacked.is_contiguous() and spacked.is_contiguous()
+    if global_scale.dtype != torch.float32 or global_scale.numel() != 1:
+        raise RuntimeError("nvfp4_gemm: global_scale must be one float32 value")
+    m, k = x.shape
+    n = qpacked.shape[0] * 16
+    if qpacked.shape[1] * 128 != k or tuple(spacked.shape) != (n // 16, k // 128, 32):
+        raise RuntimeError("nvfp4_gemm: x / qpacked / spacked shapes do not match")
+    if bias is not None and (bias.dtype != x.dtype or bias.numel() != n or not bias.is_contiguous()):
+        raise RuntimeError("nvfp4_gemm: bias must be a contiguous [N] tensor of x's dtype")
+    out = torch.empty((m, n), dtype=x.dtype, device=x.device)
+    kr = lib.sgl_mi355_nvfp4_gemm_kranges(m, n, k)
+    ws, ws_n = _workspace(x.device, kr * m * n) if kr > 1 else (None, 0)
+    check(lib.sgl_mi355_nvfp4_gemm(ptr(x), x.stride(0), ptr(qpacked), ptr(spacked), ptr(out), out.stride(0), ptr(global_scale),
+                                   ptr(bias), m, n, k, dtype_code(x.dtype), ptr(ws), ws_n, current_stream()))
+    return out
+
+
+def nvfp4_gemm_form(m: int, n: int, k: int) -> int:
+    """Which kernel nvfp4_gemm runs for this shape: 0 = weight-streaming form (M <= 64), 1 = 128x128 tile form."""
+    return int(lib.sgl_mi355_nvfp4_gemm_form(int(m), int(n), int(k)))
+
+
+def nvfp4_gemm_kranges(m: int, n: int, k: int) -> int:
+    """Split-K ranges of nvfp4_gemm for this shape (1: no slabs)."""
+    return int(lib.sgl_mi355_nvfp4_gemm_kranges(int(m), int(n), int(k)))
+
+
+def nvfp4_dequantize(weight: torch.Tensor, weight_scale: torch.Tensor, dtype, global_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Dense W [N, K] (row-major, bf16 / f16) from the checkpoint tensors, bit-exact: e2m1 nibble * e4m3 group scale, WITHOUT the
+    global scale; any K % 16 == 0.  With ``global_scale`` (f32 device scalar) each weight is T(W * global_scale) instead: one
+    rounding of the exact product, for the large-M route of PetitNvFp4LinearMethod.apply."""
+    n, k = _nvfp4_checkpoint("nvfp4_dequantize", weight, weight_scale)
+    _cuda(global_scale)
+    if global_scale is not None and (global_scale.dtype != torch.float32 or global_scale.numel() != 1):
+        raise RuntimeError("nvfp4_dequantize: global_scale must be one float32 value")
+    out = torch.empty((n, k), dtype=dtype, device=weight.device)
+    check(lib.sgl_mi355_nvfp4_dequantize(ptr(weight), ptr(weight_scale), ptr(global_scale), ptr(out), n, k, dtype_code(dtype),
+                                         current_stream()))
+    return out
+
+
 def fp8_scaled_mm(mat_a, mat_b, scales_a, scales_b, out_dtype, bias=None, out=None):
     """out[M,N] = (mat_a[M,K] @ mat_b[K,N]) * scales_a[m] * scales_b[n] (+ bias[n]).
 

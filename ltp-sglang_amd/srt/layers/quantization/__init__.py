@@ -2,10 +2,12 @@
 from .awq import AWQConfig
 from .base_config import QuantizationConfig
 from .fp8 import Fp8Config
+from .petit import PetitNvFp4Config
 from .w8a8_fp8 import W8A8Fp8Config
 from .w8a8_int8 import W8A8Int8Config
 
-QUANTIZATION_METHODS = {"fp8": Fp8Config, "w8a8_fp8": W8A8Fp8Config, "awq": AWQConfig, "w8a8_int8": W8A8Int8Config}
+QUANTIZATION_METHODS = {"fp8": Fp8Config, "w8a8_fp8": W8A8Fp8Config, "awq": AWQConfig, "w8a8_int8": W8A8Int8Config,
+                        "petit_nvfp4": PetitNvFp4Config}
 
 
 def get_quantization_config(quantization: str):
