@@ -56,7 +56,10 @@ int sgl_mi355_decode_attention(const void* q, int64_t q_stride_t, const void* k_
                                float v_scale, void* stream);
 /* kv_dtype: the q dtype, or SGL_FP8_E4M3 (3) for kv_cache_dtype = fp8_e4m3 pools (memory_pool.py:385-395; head_dim 64 / 128):
  * rows are converted exactly to the q dtype on the way into LDS, K_true = K_fp8 * k_scale, V_true = V_fp8 * v_scale
- * (RadixAttention.k_scale / v_scale, radix_attention.py:73-76; the Triton backend leaves both at 1). */
+ * (RadixAttention.k_scale / v_scale, radix_attention.py:73-76; the Triton backend leaves both at 1).
+ * MLA (DeepSeek absorbed decode; decode_attention.py Lk == 576 -> BLOCK_DMODEL 512 + BLOCK_DPE 64): head_dim 576, v_head_dim 512,
+ * one kv head, 16-bit pool, and the value buffer IS the first 512 columns of the key buffer (v_buffer == k_buffer, equal token
+ * strides; MLATokenToKVPool.get_value_buffer) -- every latent row is read once and serves QK^T and PV.  Any num_q_heads. */
 
 /* decode_attention_fwd (stage 1) with stage 2 done IN THE SAME LAUNCH: the last workgroup of each request to finish merges the
  * request's splits (decode_attention.py:492-552), writes the merged row (out_o, optional) and its per-token fp8 quantisation
@@ -177,6 +180,12 @@ int sgl_mi355_set_kv_buffer_fp8(void* k_buffer, void* v_buffer, int64_t k_slot_b
                                 const void* cache_k, const void* cache_v, int64_t cache_k_stride, int64_t cache_v_stride,
                                 int k_row, int v_row, int64_t tokens, int src_dtype, float k_scale, float v_scale,
                                 void* stream);
+/* MLATokenToKVPool.set_mla_kv_buffer -> set_mla_kv_buffer_triton, mem_cache/memory_pool.py:643-705: kv_buffer[loc[i], 0, :nope] =
+ * cache_k_nope[i] and kv_buffer[loc[i], 0, nope:nope + rope] = cache_k_rope[i] (the DeepSeek latent row: kv_lora_rank + qk_rope_head_dim
+ * = 512 + 64 columns) in one launch.  Row sizes, the two sources' row strides and the pool's slot stride in bytes, multiples of 16. */
+int sgl_mi355_set_mla_kv_buffer(void* kv_buffer, int64_t slot_bytes, const int64_t* loc, const void* cache_k_nope,
+                                const void* cache_k_rope, int64_t nope_stride_bytes, int64_t rope_stride_bytes,
+                                int nope_row_bytes, int rope_row_bytes, int64_t tokens, void* stream);
 /* MHATokenToKVPool.move_kv_cache -> copy_all_layer_kv_cache (memory_pool.py:409-417, 1046-1081): buf[tgt_loc[i]] = buf[src_loc[i]]
  * for every buffer in data_ptrs (uint64 [num_buffers], device) with rows of data_strides[b] bytes (int64 [num_buffers], device;
  * multiples of 16), in place: every source row of a column block is read before any target row of it is written, as in the

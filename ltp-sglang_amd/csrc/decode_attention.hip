@@ -24,62 +24,12 @@
 //  * partial results use the reference's own scratch layout (attn_logits f32
 //    [bs, Hq, max_splits, Dv] holding acc/l, attn_lse f32 [bs, Hq, max_splits] holding
 //    m + log(l)) and stage 2 merges the splits by LSE exactly like _fwd_kernel_stage2.
+#include <type_traits>
+
+#include "decode_params.h"   // DecodeParams, kTile, request_range, split_len, softcap_log2 (shared with mla_decode_attention.hip)
 #include "row_helpers.h"
 
 namespace {
-
-struct DecodeParams {
-  const void* q;
-  int64_t q_stride_t;  // elements between tokens of q; heads are contiguous [Hq, D]
-  const void* k_buf;
-  const void* v_buf;
-  int64_t k_stride_t, k_stride_h, v_stride_t, v_stride_h;  // elements
-  void* o;
-  int64_t o_stride_t;
-  // index mode A (Triton backend metadata): kv_indptr/kv_indices
-  const int32_t* kv_indptr;
-  const int32_t* kv_indices;
-  // index mode B (CPU op schema): req_to_token[req_pool_indices[b], :seq_lens[b]]
-  const int32_t* req_to_token;
-  int64_t req_to_token_stride;
-  const int64_t* req_pool_indices;
-  const int64_t* seq_lens;
-  float* attn_logits;
-  float* attn_lse;
-  const int32_t* num_kv_splits;
-  int max_kv_splits;
-  int bs, hq, hkv, group, dv;
-  float sm_scale, logit_cap;
-  int kv_fp8;             // K/V pool rows are e4m3fn bytes (kv_cache_dtype fp8_e4m3, memory_pool.py:385-395), else the q dtype
-  float k_scale, v_scale;  // K_true = K_fp8 * k_scale, V_true = V_fp8 * v_scale (radix_attention.py:73-76); 1 for 16-bit pools
-  // in-launch stage 2 (MODE 0): the last workgroup of a request to finish merges its splits and quantises the row
-  int32_t* merge_cnt;  // [bs], zero on entry, left zero; NULL = off
-  void* mq_o;          // optional T [bs, Hq * Dv]
-  void* mq_q;          // optional e4m3 [bs, Hq * Dv] with mq_s f32 [bs]
-  float* mq_s;
-  // Cascade shared-prefix decode: all `bs` requests share the first prefix_len slots of their sequences.
-  //   prefix pass  a launch of the EXTEND kernel (extend_attention.hip, ExtendParams::casc_*): the bs decode queries are the
-  //                query block, the shared rows the keys, staged once per (kv head, 32 requests, split) in LDS for all 4 x 32
-  //                (head, request) pairs of a workgroup; prefix_splits split partials (O = acc / l, LSE) per (request, head)
-  //                go to the TOP split slots [max_kv_splits - prefix_splits, max_kv_splits).  (Round 2 first ran the prefix as
-  //                16-column chunks of this kernel -- every chunk re-read the rows, 19.6 us at 64 x 1536 -- and then had the
-  //                merging workgroup of every request read prefix + suffix partials, +2 us per prefix split.)
-  //   suffix pass  (CASC = 2, prefix_splits > 0): the ordinary kernel over every request's private slots, except that split 0
-  //                of every (request, kv head) CONTINUES the online softmax from the prefix state (the LSE-weighted sum of the
-  //                prefix partials is its initial (m, l, acc) -- the math of merge_state, merge_attn_states.cu, applied before
-  //                instead of after), so the in-launch merge sees suffix slots only.
-  int prefix_len, prefix_splits;
-  // Flat unit list (round 5, SCHED kernels; csrc/kv_index.hip decode_schedule_kernel): the (request, split) units of the launch as a
-  // list sorted by length, longest first -- grid y walks the list, so the dispatcher starts the long units first and fills the
-  // chip's slots with short ones as they free up (ragged batches), and the grid carries no never-live workgroups.
-  // sched: {T, units, total tokens, capacity}, then per unit {request, split | splits << 16, kv_indptr[request], its length}.
-  // sched_chunks = grid y = the capacity the host sized the list for.
-  const int32_t* sched;
-  int sched_chunks;
-#ifdef SGL_DEC_TIMELINE
-  long long* tl;   // tools/debug/dec_timeline.py: s_memrealtime stamps [workgroup (linear)][wave][8]
-#endif
-};
 
 #ifdef SGL_DEC_TIMELINE
 long long* g_dec_tl = nullptr;
@@ -92,34 +42,6 @@ long long* g_dec_tl = nullptr;
 #else
 #define DEC_STAMP(k) do { } while (0)
 #endif
-
-constexpr int kTile = 32;  // tokens per wave tile == reference _MIN_BLOCK_KV (decode_attention.py:35)
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
-
-__device__ __forceinline__ void request_range(const DecodeParams& p, int b, const int32_t*& idx_row, int& seq_len) {
-  if (p.kv_indptr != nullptr) {
-    const int s0 = p.kv_indptr[b];
-    seq_len = p.kv_indptr[b + 1] - s0;
-    idx_row = p.kv_indices + s0;
-  } else {
-    seq_len = (int)p.seq_lens[b];
-    idx_row = p.req_to_token + p.req_pool_indices[b] * p.req_to_token_stride;
-  }
-}
-
-__device__ __forceinline__ int split_len(int seq_len, int nsplit) {
-  // decode_attention.py:90-94: ceil(ceil(seq/splits)/MIN_BLOCK_KV)*MIN_BLOCK_KV
-  const int per = (seq_len + nsplit - 1) / nsplit;
-  return (per + kTile - 1) / kTile * kTile;
-}
-
-__device__ __forceinline__ float softcap_log2(float s_scaled, float cap) {
-  // cap * tanh(x / cap), tanh(y) = 2*sigmoid(2y) - 1 (decode_attention.py:38-41)
-  const float y = s_scaled / cap;
-  const float t = 2.0f / (1.0f + __expf(-2.0f * y)) - 1.0f;
-  return cap * t * kLog2e;
-}
 
 // Memory-model note: the hand-off below is the first row of the "hand-offs measured with sc1 loads / one agent-scope atomic
 // add per storing workgroup" table of the CDNA4 guide (MI355X_MICROARCH.md, Workgroup dispatch ... inter-workgroup visibility)
@@ -746,6 +668,8 @@ int launch_all(const DecodeParams& p, int d_qk, hipStream_t st) {
     rc = p.kv_fp8 ? launch_mfma<T, 128, 1>(p, st) : launch_mfma<T, 128, 2>(p, st);
   } else if (d_qk == p.dv && d_qk == 64) {
     rc = p.kv_fp8 ? launch_mfma<T, 64, 1>(p, st) : launch_mfma<T, 64, 2>(p, st);
+  } else if (d_qk == 576 && p.dv == 512 && p.hkv == 1) {  // MLA latent rows (mla_decode_attention.hip)
+    rc = launch_mla_decode(p, std::is_same<T, __bf16>::value ? SGL_BF16 : SGL_F16, st);
   } else {
     dim3 grid(p.hq, p.max_kv_splits, p.bs);
     hipLaunchKernelGGL((decode_attn_stage1_generic<T>), grid, dim3(64), 0, st, p, d_qk);
@@ -789,7 +713,10 @@ static int decode_entry(
             "decode_attention: need either (kv_indptr, kv_indices) or (req_to_token, req_pool_indices, seq_lens)");
   SGL_CHECK(num_kv_heads > 0 && num_q_heads % num_kv_heads == 0, "decode_attention: Hq=%d not a multiple of Hkv=%d",
             num_q_heads, num_kv_heads);
-  SGL_CHECK(head_dim > 0 && head_dim <= 256 && v_head_dim > 0 && v_head_dim <= 256,
+  // DeepSeek-V2 / V3 absorbed MLA decode: one shared latent row per token, kv_lora_rank + qk_rope_head_dim = 512 + 64 columns, the
+  // value its first 512 (decode_attention.py: Lk == 576 -> BLOCK_DMODEL 512, BLOCK_DPE 64; MLATokenToKVPool, memory_pool.py:708-853)
+  const bool mla = head_dim == 576 && v_head_dim == 512 && num_kv_heads == 1;
+  SGL_CHECK(mla || (head_dim > 0 && head_dim <= 256 && v_head_dim > 0 && v_head_dim <= 256),
             "decode_attention: head dims (%d, %d) outside (0, 256]", head_dim, v_head_dim);
   SGL_CHECK(max_kv_splits >= 1 && max_kv_splits <= 65535, "decode_attention: max_kv_splits=%d out of range",
             max_kv_splits);
@@ -797,6 +724,16 @@ static int decode_entry(
   SGL_CHECK(dtype == SGL_BF16 || dtype == SGL_F16, "decode_attention: dtype code %d unsupported (bf16=0, f16=1)", dtype);
   SGL_CHECK(kv_dtype == dtype || kv_dtype == SGL_FP8_E4M3, "decode_attention: kv_dtype %d must be the q dtype or fp8_e4m3", kv_dtype);
   const bool kv8 = kv_dtype == SGL_FP8_E4M3;
+  if (mla) {
+    SGL_CHECK(!kv8, "decode_attention: the 576 / 512 MLA latent pool must be 16-bit (bf16 / f16); an fp8_e4m3 latent cache is not served");
+    SGL_CHECK(v_buffer == k_buffer && v_stride_t == k_stride_t,
+              "decode_attention: with head dims (576, 512) on one kv head the value buffer must be the first 512 columns of the key "
+              "buffer (v_buffer == k_buffer, equal token strides)");
+    SGL_CHECK(kv_indptr != nullptr || req_to_token != nullptr, "decode_attention: null index pointer");
+    SGL_CHECK(k_stride_t % 8 == 0 && q_stride_t % 8 == 0 && ((uintptr_t)k_buffer % 16) == 0 && ((uintptr_t)q % 16) == 0 &&
+                  ((uintptr_t)attn_logits % 16) == 0,
+              "decode_attention: q / latent rows / attn_logits must be 16-byte aligned for the MLA kernel");
+  }
   SGL_CHECK(!kv8 || (head_dim == v_head_dim && (head_dim == 128 || head_dim == 64)),
             "decode_attention: the fp8 KV cache needs head_dim == v_head_dim in {64, 128} (got %d, %d)", head_dim, v_head_dim);
   SGL_CHECK(!kv8 || (k_stride_t % 16 == 0 && v_stride_t % 16 == 0 && k_stride_h % 16 == 0 && v_stride_h % 16 == 0),

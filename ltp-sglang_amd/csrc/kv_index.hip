@@ -409,6 +409,43 @@ extern "C" int sgl_mi355_set_kv_buffer(void* k_buffer, void* v_buffer, int64_t k
   return SGL_MI355_OK;
 }
 
+// MLATokenToKVPool.set_mla_kv_buffer (memory_pool.py:643-705, set_mla_kv_buffer_kernel): the latent row of token t is
+// k_nope[t] (kv_lora_rank columns) followed by k_rope[t] (qk_rope_head_dim columns), two sources with their own row strides.
+// One wave per token, 16-byte loads and stores; a 1 152-byte row is 72 pieces: one pass of the wave and a 8-lane second one.
+namespace {
+__global__ __launch_bounds__(256) void set_mla_kv_buffer_kernel(char* kv_buf, int64_t slot_bytes, const int64_t* loc, const char* nope,
+                                                                const char* rope, int64_t nope_stride_bytes, int64_t rope_stride_bytes,
+                                                                int nope_row_bytes, int rope_row_bytes, int64_t tokens) {
+  const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= tokens) return;
+  const int lane = threadIdx.x & 63;
+  char* dst = kv_buf + loc[t] * slot_bytes;
+  const char* ns = nope + t * nope_stride_bytes;
+  const char* rs = rope + t * rope_stride_bytes;
+  for (int o = lane * 16; o < nope_row_bytes + rope_row_bytes; o += 64 * 16)
+    *(u32x4_t*)(dst + o) = *(const u32x4_t*)(o < nope_row_bytes ? ns + o : rs + (o - nope_row_bytes));
+}
+}  // namespace
+
+// kv_buffer: one layer's [slots, 1, nope + rope] pool, slot stride in bytes; cache_k_nope / cache_k_rope: [tokens, row] with byte strides.
+extern "C" int sgl_mi355_set_mla_kv_buffer(void* kv_buffer, int64_t slot_bytes, const int64_t* loc, const void* cache_k_nope,
+                                           const void* cache_k_rope, int64_t nope_stride_bytes, int64_t rope_stride_bytes,
+                                           int nope_row_bytes, int rope_row_bytes, int64_t tokens, void* stream) {
+  SGL_CHECK(tokens >= 0, "set_mla_kv_buffer: negative token count");
+  if (tokens == 0) return SGL_MI355_OK;
+  SGL_CHECK(kv_buffer && loc && cache_k_nope && cache_k_rope, "set_mla_kv_buffer: null pointer");
+  SGL_CHECK(nope_row_bytes > 0 && rope_row_bytes > 0 && nope_row_bytes % 16 == 0 && rope_row_bytes % 16 == 0 && slot_bytes % 16 == 0 &&
+                slot_bytes >= nope_row_bytes + rope_row_bytes && nope_stride_bytes % 16 == 0 && rope_stride_bytes % 16 == 0 &&
+                ((uintptr_t)kv_buffer % 16) == 0 && ((uintptr_t)cache_k_nope % 16) == 0 && ((uintptr_t)cache_k_rope % 16) == 0,
+            "set_mla_kv_buffer: rows must be 16-byte aligned and fit the slot (nope_row_bytes=%d, rope_row_bytes=%d, slot_bytes=%lld)",
+            nope_row_bytes, rope_row_bytes, (long long)slot_bytes);
+  hipLaunchKernelGGL(set_mla_kv_buffer_kernel, dim3((unsigned)((tokens + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (char*)kv_buffer,
+                     slot_bytes, loc, (const char*)cache_k_nope, (const char*)cache_k_rope, nope_stride_bytes, rope_stride_bytes,
+                     nope_row_bytes, rope_row_bytes, tokens);
+  SGL_HIP_LAUNCH_CHECK();
+  return SGL_MI355_OK;
+}
+
 // kv_indptr and/or num_kv_splits may be NULL to skip that part.  static_splits: 0 = the reference's heuristic
 // (get_num_kv_splits_triton), 1 = max_kv_splits for every request (SGLANG_TRITON_DECODE_ATTN_STATIC_KV_SPLITS),
 // 2 = the MI355X balance rule (any split count gives the same attention up to fp association: SURVEY.md a12).

@@ -76,6 +76,7 @@ from .kvcache import (
     get_last_loc,
     move_kv_cache,
     set_kv_buffer,
+    set_mla_kv_buffer,
     write_req_to_token,
 )
 from .torch_ops import register as register_torch_ops

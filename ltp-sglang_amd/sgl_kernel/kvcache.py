@@ -82,6 +82,19 @@ def set_kv_buffer(k_buffer, v_buffer, loc, cache_k, cache_v, k_scale=None, v_sca
                                       cv.shape[1] * es, t, current_stream()))
 
 
+def set_mla_kv_buffer(kv_buffer, loc, cache_k_nope, cache_k_rope) -> None:
+    """kv_buffer[loc, 0, :nope] = cache_k_nope ; kv_buffer[loc, 0, nope:] = cache_k_rope for one layer's [slots, 1, nope + rope]
+    latent pool (set_mla_kv_buffer_triton, memory_pool.py:681-705); the two sources keep their own row strides."""
+    t = loc.numel()
+    kn, kr = cache_k_nope.reshape(t, -1), cache_k_rope.reshape(t, -1)
+    assert loc.dtype == torch.int64 and loc.is_contiguous()
+    assert kn.stride(1) == 1 and kr.stride(1) == 1 and kv_buffer[0].is_contiguous()
+    assert kv_buffer.dtype == kn.dtype == kr.dtype and kv_buffer[0].numel() == kn.shape[1] + kr.shape[1]
+    es = kv_buffer.element_size()
+    check(lib.sgl_mi355_set_mla_kv_buffer(ptr(kv_buffer), kv_buffer.stride(0) * es, ptr(loc), ptr(kn), ptr(kr), kn.stride(0) * es,
+                                          kr.stride(0) * es, kn.shape[1] * es, kr.shape[1] * es, t, current_stream()))
+
+
 def move_kv_cache(data_ptrs, data_strides, max_stride_bytes: int, tgt_loc, src_loc) -> None:
     """buf[tgt_loc] = buf[src_loc] (rows of data_strides[b] bytes) for every buffer address in data_ptrs, in place: all source
     rows are read before any target row is written (copy_all_layer_kv_cache, memory_pool.py:1046-1081).  More than 4096

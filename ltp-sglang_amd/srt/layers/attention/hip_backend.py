@@ -84,6 +84,12 @@ class HipAttnBackend(AttentionBackend):
         self.kv_sched_rounds_pct = int(getattr(args, "kv_sched_rounds_pct", 150))
         self.v_head_dim = model_runner.token_to_kv_pool.get_value_buffer(0).shape[-1]
         self.qk_head_dim = model_runner.token_to_kv_pool.get_key_buffer(0).shape[-1]
+        if (self.qk_head_dim, self.v_head_dim, self.num_kv_head) == (576, 512, 1):
+            # MLA latent pool: the decode kernel's unit is a head block of up to 64 heads (csrc/mla_decode_attention.hip), not a
+            # 16-head chunk -- the split rule counts 16 heads per unit, so it is given 16 heads per head block
+            self.num_head_for_splits = 16 * (1 if self.num_head <= 32 else (self.num_head + 63) // 64)
+        else:
+            self.num_head_for_splits = self.num_head
         self.max_context_len = cfg.context_len
         gpu_id = getattr(model_runner, "gpu_id", 0)
         self.device_core_count = lib.sgl_mi355_device_cu_count(int(gpu_id))  # 256 on MI355X
@@ -140,7 +146,7 @@ class HipAttnBackend(AttentionBackend):
                               self.kv_sched_rounds_pct)
         else:
             # one launch: kv_indptr[1:bs+1] = cumsum(seq_lens) and the per-request split heuristic
-            K.decode_metadata(kv_indptr, num_kv_splits, seq_lens, 1, self.num_head, self.num_kv_head, self.max_kv_splits,
+            K.decode_metadata(kv_indptr, num_kv_splits, seq_lens, 1, self.num_head_for_splits, self.num_kv_head, self.max_kv_splits,
                               self.device_core_count, self.static_kv_splits)
         if kv_indices is None:
             kv_indices = torch.empty(seq_lens_sum, dtype=torch.int32, device=self.device)

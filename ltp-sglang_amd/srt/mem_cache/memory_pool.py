@@ -1,7 +1,7 @@
-"""Request->token table and the per-layer MHA KV pool.
+"""Request->token table, the per-layer MHA KV pool and the MLA latent pool.
 
-Follows python/sglang/srt/mem_cache/memory_pool.py: ReqToTokenPool (:47-94), KVCache (:97-150) and
-MHATokenToKVPool (:162-417).  Layout contract kept bit-for-bit:
+Follows python/sglang/srt/mem_cache/memory_pool.py: ReqToTokenPool (:47-94), KVCache (:97-150),
+MHATokenToKVPool (:162-417) and MLATokenToKVPool (:708-853).  Layout contract kept bit-for-bit:
   * req_to_token is int32 [size, max_context_len], zero-initialised, with a FIFO free list of request rows;
   * every layer has k_buffer/v_buffer of shape [size + page_size, head_num, head_dim]; slot 0 is the padding
     sink that padded tokens write to and the allocator never hands out (:222-227).
@@ -130,3 +130,50 @@ class MHATokenToKVPool(KVCache):
         from ...sgl_kernel import move_kv_cache
 
         move_kv_cache(self.data_ptrs, self.data_strides, self.head_num * self.head_dim * self._kv.element_size(), tgt_loc, src_loc)
+
+
+class MLATokenToKVPool(KVCache):
+    """The latent KV pool of multi-head latent attention (DeepSeek-V2 / V3 / R1), memory_pool.py:708-853: one
+    [size + page_size, 1, kv_lora_rank + qk_rope_head_dim] tensor per layer; the key of a token is its whole row, the value the
+    first kv_lora_rank columns of the SAME row (a view -- the decode kernel reads every row once for both).  16-bit dtypes."""
+
+    def __init__(self, size: int, page_size: int, dtype: torch.dtype, kv_lora_rank: int, qk_rope_head_dim: int, layer_num: int,
+                 device: str, enable_memory_saver: bool, start_layer: Optional[int] = None, end_layer: Optional[int] = None):
+        super().__init__(size, page_size, dtype, layer_num, device, start_layer, end_layer)
+        if dtype not in (torch.bfloat16, torch.float16):
+            raise ValueError(f"MLATokenToKVPool: 16-bit dtypes only (bf16 / f16), got {dtype}")
+        self.kv_lora_rank = kv_lora_rank
+        self.qk_rope_head_dim = qk_rope_head_dim
+        # slot 0 is the padding sink that padded tokens write to (:755-763)
+        self.kv_buffer = [torch.zeros((size + page_size, 1, kv_lora_rank + qk_rope_head_dim), dtype=self.store_dtype, device=device)
+                          for _ in range(layer_num)]
+        self.data_ptrs = torch.tensor([x.data_ptr() for x in self.kv_buffer], dtype=torch.uint64, device=device)
+        self.layer_transfer_counter = None
+        self.mem_usage = self.get_kv_size_bytes() / (1 << 30)
+
+    def get_kv_size_bytes(self) -> int:
+        return sum(x.numel() * x.element_size() for x in self.kv_buffer)
+
+    def get_key_buffer(self, layer_id: int):
+        if self.layer_transfer_counter is not None:
+            self.layer_transfer_counter.wait_until(layer_id - self.start_layer)
+        return self.kv_buffer[layer_id - self.start_layer]
+
+    def get_value_buffer(self, layer_id: int):
+        return self.get_key_buffer(layer_id)[..., : self.kv_lora_rank]
+
+    def get_kv_buffer(self, layer_id: int):
+        return self.get_key_buffer(layer_id), self.get_value_buffer(layer_id)
+
+    def set_kv_buffer(self, layer, loc: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor,
+                      k_scale: Optional[float] = None, v_scale: Optional[float] = None):
+        """pool[layer][loc] = cache_k, the whole latent row (:819-834); cache_v is its head and is not stored again."""
+        self.set_mla_kv_buffer(layer, loc, cache_k[..., : self.kv_lora_rank], cache_k[..., self.kv_lora_rank:])
+
+    def set_mla_kv_buffer(self, layer, loc: torch.Tensor, cache_k_nope: torch.Tensor, cache_k_rope: torch.Tensor):
+        """pool[layer][loc, 0, :kv_lora_rank] = cache_k_nope ; [kv_lora_rank:] = cache_k_rope (:836-853): one HIP launch."""
+        from ...sgl_kernel import set_mla_kv_buffer
+
+        if cache_k_nope.dtype != self.dtype:
+            cache_k_nope, cache_k_rope = cache_k_nope.to(self.dtype), cache_k_rope.to(self.dtype)
+        set_mla_kv_buffer(self.kv_buffer[layer.layer_id - self.start_layer], loc, cache_k_nope, cache_k_rope)
