@@ -131,7 +131,14 @@ int sgl_mi355_extend_attention_set_kv_hint(int mean_keys_per_query_block);
  * custom_mask (u8 / bool, request b's [ext_len, prefix_len + ext_len] block at mask_indptr[b]; NULL = none),
  * skip_prefix_custom_mask and sliding_window_size (<= 0 = none) follow extend_attention.py:131-203 (prefix phase: mask
  * unless skipped, window q_idx <= kv_idx + W over the kv_indices the caller windowed, triton_backend.py:927-955) and
- * :205-284 (extend phase: the custom mask REPLACES the causal rule). */
+ * :205-284 (extend phase: the custom mask REPLACES the causal rule).
+ * MLA latent rows: (head_dim, v_head_dim, num_kv_heads) == (576, 512, 1) is the absorbed DeepSeek-V2 / V3 / R1 extend
+ * (extend_attention.py:336-338: Lq == 576 -> BLOCK_DMODEL 512 + BLOCK_DPE 64; called as attn_mqa(q, k, k_nope),
+ * python/sglang/srt/models/deepseek_v2.py:1275-1277), served by csrc/mla_extend_attention.hip: q [T, Hq, 576], o [T, Hq, 512],
+ * k_extend [T, 1, 576], bf16 / f16, both addressing modes, is_causal 0 / 1, logit_cap.  The value is ALWAYS the first 512 columns
+ * of the key row: v_extend == k_extend with equal token strides, and v_buffer == k_buffer with equal token strides (both NULL
+ * when no request has a prefix); anything else, a custom_mask, a sliding window or an fp8 pool is an argument error.  Other head
+ * dims above 256 are refused. */
 int sgl_mi355_extend_attention(const void* q_extend, const void* k_extend, const void* v_extend, void* o_extend,
                                int64_t q_stride_t, int64_t k_stride_t_ext, int64_t v_stride_t_ext, int64_t o_stride_t,
                                const void* k_buffer, const void* v_buffer, int64_t k_stride_t, int64_t k_stride_h,

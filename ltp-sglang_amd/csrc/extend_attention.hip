@@ -928,6 +928,8 @@ template <typename T>
 int launch_all(ExtendParams& p, int d_qk, int dv, int total_q, int max_len_extend, hipStream_t st) {
   if (d_qk == dv && d_qk == 128) return p.kv_fp8 ? launch_mfma<T, 128, true>(p, max_len_extend, st) : launch_mfma<T, 128, false>(p, max_len_extend, st);
   if (d_qk == dv && d_qk == 64) return p.kv_fp8 ? launch_mfma<T, 64, true>(p, max_len_extend, st) : launch_mfma<T, 64, false>(p, max_len_extend, st);
+  if (d_qk == 576 && dv == 512 && p.hkv == 1)  // MLA latent rows (mla_extend_attention.hip)
+    return launch_mla_extend(p, max_len_extend, std::is_same<T, __bf16>::value ? SGL_BF16 : SGL_F16, st);
   hipLaunchKernelGGL((extend_attn_generic<T>), dim3(total_q, p.hq), dim3(64), 0, st, p, d_qk, dv, total_q);
   SGL_HIP_LAUNCH_CHECK();
   return SGL_MI355_OK;
@@ -999,7 +1001,10 @@ extern "C" int sgl_mi355_extend_attention(
             "extend_seq_lens, extend_start_loc)");
   SGL_CHECK(num_kv_heads > 0 && num_q_heads % num_kv_heads == 0, "extend_attention: Hq=%d not a multiple of Hkv=%d",
             num_q_heads, num_kv_heads);
-  SGL_CHECK(head_dim > 0 && head_dim <= 256 && v_head_dim > 0 && v_head_dim <= 256,
+  // DeepSeek-V2 / V3 absorbed MLA extend: one shared latent row per token, kv_lora_rank + qk_rope_head_dim = 512 + 64 columns, the
+  // value its first 512 (extend_attention.py:336-338: Lq == 576 -> BLOCK_DMODEL 512, BLOCK_DPE 64; deepseek_v2.py:1275-1277)
+  const bool mla = head_dim == 576 && v_head_dim == 512 && num_kv_heads == 1;
+  SGL_CHECK(mla || (head_dim > 0 && head_dim <= 256 && v_head_dim > 0 && v_head_dim <= 256),
             "extend_attention: head dims (%d, %d) outside (0, 256]", head_dim, v_head_dim);
   SGL_CHECK(dtype == SGL_BF16 || dtype == SGL_F16, "extend_attention: dtype code %d unsupported (bf16=0, f16=1)", dtype);
   SGL_CHECK(kv_dtype == dtype || kv_dtype == SGL_FP8_E4M3, "extend_attention: kv_dtype %d must be the q dtype or fp8_e4m3", kv_dtype);
@@ -1013,6 +1018,23 @@ extern "C" int sgl_mi355_extend_attention(
                   ((uintptr_t)o_extend % 8) == 0 && (!k_buffer || ((uintptr_t)k_buffer % 16) == 0) &&
                   (!v_buffer || ((uintptr_t)v_buffer % 16) == 0),
               "extend_attention: rows must be 16-byte aligned for the MFMA path");
+  }
+  if (mla) {
+    SGL_CHECK(custom_mask == nullptr,
+              "extend_attention: head dims (576, 512) on one kv head (MLA) take no custom_mask (target-verify is not served for this shape)");
+    SGL_CHECK(sliding_window_size <= 0,
+              "extend_attention: head dims (576, 512) on one kv head (MLA) take no sliding window (got sliding_window_size=%d)",
+              sliding_window_size);
+    SGL_CHECK(v_extend == k_extend && v_stride_t_ext == k_stride_t_ext,
+              "extend_attention: with head dims (576, 512) on one kv head v_extend must be the first 512 columns of k_extend "
+              "(v_extend == k_extend, equal token strides)");
+    SGL_CHECK(v_buffer == k_buffer && (k_buffer == nullptr || v_stride_t == k_stride_t),
+              "extend_attention: with head dims (576, 512) on one kv head the value buffer must be the first 512 columns of the key "
+              "buffer (v_buffer == k_buffer, equal token strides)");
+    SGL_CHECK(q_stride_t % 8 == 0 && k_stride_t_ext % 8 == 0 && o_stride_t % 4 == 0 && k_stride_t % 8 == 0 &&
+                  ((uintptr_t)q_extend % 16) == 0 && ((uintptr_t)k_extend % 16) == 0 && ((uintptr_t)o_extend % 8) == 0 &&
+                  ((uintptr_t)k_buffer % 16) == 0,
+              "extend_attention: rows must be 16-byte aligned for the MLA path");
   }
   ExtendParams p;
   p.q = q_extend; p.ke = k_extend; p.ve = v_extend; p.o = o_extend;

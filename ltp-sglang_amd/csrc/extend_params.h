@@ -56,3 +56,8 @@ constexpr float kLog2e = 1.4426950408889634f;
 // returns SGL_MI355_OK after a launch.  The caller has checked eligibility with extend_phased_eligible.
 bool extend_phased_eligible(const ExtendParams& p);
 int launch_extend_phased(ExtendParams& p, int max_len_extend, int dtype, hipStream_t st);
+
+// mla_extend_attention.hip: the 576 / 512 latent-KV (MLA) extend, one kv head, V = the first 512 columns of K (pool rows and new
+// rows alike; ve / v_buf are not read).  dtype: SGL_BF16 / SGL_F16.  Returns SGL_MI355_OK after a launch; the caller
+// (sgl_mi355_extend_attention) has checked the shape, the aliasing and that no mask / window / fp8 pool is asked for.
+int launch_mla_extend(const ExtendParams& p, int max_len_extend, int dtype, hipStream_t st);

@@ -101,7 +101,9 @@ def extend_attention_fwd(
     t, hq, d = q_extend.shape
     hkv, dv = v_extend.shape[1], v_extend.shape[2]
     assert q_extend.stride(2) == 1 and q_extend.stride(1) == d and o_extend.stride(1) == dv
-    assert k_extend.stride(1) == d and v_extend.stride(1) == dv and k_extend.stride(2) == 1 and v_extend.stride(2) == 1
+    # (a head dimension of size 1 has no stride to check: the MLA value k_extend[..., :512] is a [T, 1, 512] view with stride(1) 576)
+    assert hkv == 1 or (k_extend.stride(1) == d and v_extend.stride(1) == dv)
+    assert k_extend.stride(2) == 1 and v_extend.stride(2) == 1
     assert qo_indptr.dtype == torch.int32 and kv_indptr.dtype == torch.int32 and kv_indices.dtype == torch.int32
     # (k_buffer / v_buffer None: no request of the batch has a cached prefix -- nothing is read from the pool, whatever its dtype)
     kst, ksh = _row_strides(k_buffer) if k_buffer is not None else (0, 0)

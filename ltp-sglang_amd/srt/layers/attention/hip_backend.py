@@ -343,8 +343,17 @@ class HipAttnBackend(AttentionBackend):
         # no cached prefix anywhere in the batch (the size of kv_indices is host knowledge): nothing is read from the pool, so the
         # kernel need not know its dtype -- an fp8 pool would otherwise select the fp8-prefix instantiation for rows that do not exist
         no_prefix = kv_indices.numel() == 0
+        k_rows = _rows(k)
+        if (self.qk_head_dim, self.v_head_dim, self.num_kv_head) == (576, 512, 1):
+            # MLA latent pool: the value IS the first 512 columns of the key row, and the kernel reads it from there (it takes no
+            # separate value).  The caller's v is ignored: MLATokenToKVPool.set_kv_buffer drops cache_v and stores only cache_k, so
+            # the pool never held it, and the reference's caller passes k_nope, whose bits equal k[..., :512]
+            # (deepseek_v2.py:1275-1277: attn_mqa(q, k, k_nope)).
+            v_rows = k_rows[..., :512]
+        else:
+            v_rows = _rows(v)
         K.extend_attention_fwd(
-            q.view(-1, layer.tp_q_head_num, layer.qk_head_dim), _rows(k), _rows(v),
+            q.view(-1, layer.tp_q_head_num, layer.qk_head_dim), k_rows, v_rows,
             o.view(-1, layer.tp_q_head_num, layer.v_head_dim),
             None if no_prefix else forward_batch.token_to_kv_pool.get_key_buffer(layer.layer_id),
             None if no_prefix else forward_batch.token_to_kv_pool.get_value_buffer(layer.layer_id),
