@@ -609,6 +609,48 @@ int sgl_mi355_car_all_reduce_add_rmsnorm_quant_slabs(const float* slabs, int nsl
 int sgl_mi355_car_all_gather(const void* in, void* out, int64_t rows, int64_t row_bytes, const void* const* peer_bufs, int rank,
                              int world, int64_t max_bytes, void* stream);
 
+/* ---- fused MoE for unquantised 16-bit experts (bf16 / f16) -------------------------------------
+ * fused_experts_impl (python/sglang/srt/layers/moe/fused_moe_triton/fused_moe.py:1391-1631): align, grouped GEMM 1 +
+ * SiluAndMul, grouped GEMM 2 * router weight, sum over topk.  A "pair" is p = token * topk + j, P = num_tokens * topk.
+ * Everything below is asynchronous on stream, allocation- and sync-free and reads no device value on the host: the chain is
+ * HIP-graph capturable and a replay follows new routing. */
+/* topk_softmax (sgl-kernel/python/sgl_kernel/moe.py:28-36; python/sglang/srt/layers/moe/topk.py:335-361): softmax over the
+ * num_experts <= 512 logits of every row in f32, the topk <= min(num_experts, 32) largest (ties: the lower index), weights
+ * f32 [T, topk] (divided by their sum with renormalize), ids int32 [T, topk].  dtype: of gating_output (f32 / bf16 / f16). */
+int sgl_mi355_topk_softmax(float* topk_weights, int* topk_ids, const void* gating_output, int num_tokens, int num_experts,
+                           int topk, int renormalize, int dtype, void* stream);
+/* moe_align_block_size (sgl-kernel/python/sgl_kernel/moe.py:6-25; layout: fused_moe.py:549-619): every expert's pairs, ASCENDING,
+ * padded to a multiple of block_size with the value num_pairs; experts_ids: one expert per block; num_tokens_post_pad[0]: the
+ * padded total; cumsum_buffer [num_experts + 1]: where every expert's run starts.  Ids outside [0, num_experts) are left out.
+ * sorted_capacity >= num_pairs + min(num_experts, num_pairs) * (block_size - 1) entries; entries past the padded total are
+ * written (with num_pairs) only when pad_sorted_token_ids is set.  num_experts <= 1024.  workspace: the int32 count reported
+ * by the _workspace_ints entry point below (0 up to 4096 pairs: one workgroup). */
+int sgl_mi355_moe_align_block_size(const int* topk_ids, int64_t num_pairs, int num_experts, int block_size,
+                                   int* sorted_token_ids, int64_t sorted_capacity, int* experts_ids, int* num_tokens_post_pad,
+                                   int* cumsum_buffer, int pad_sorted_token_ids, int* workspace, int64_t workspace_ints,
+                                   void* stream);
+int64_t sgl_mi355_moe_align_workspace_ints(int64_t num_pairs, int num_experts);
+/* invoke_fused_moe_kernel (fused_moe.py:622-780) over that layout: out[p][n] = epilogue(sum_k a[p / a_rows_div][k] * w[e(p)][n][k])
+ * for every pair p the layout holds; a [*, K], out [num_pairs, N], both contiguous in dtype (bf16 / f16).
+ *   epilogue 1 (GEMM 1 + silu_and_mul, fused_moe.py:1518-1547): w [E, 2 N, K], rows [0, N) gate and [N, 2 N) up;
+ *              out = silu(gate) * up, rounded once; topk_weights[p], when given (apply_router_weight_on_input), multiplies
+ *              gate and up first, as the reference multiplies GEMM 1's product.
+ *   epilogue 0 (GEMM 2, fused_moe.py:1558-1584): w [E, N, K]; out = sum (* topk_weights[p] when given), rounded once.
+ * block_size is the one the layout was built with and selects the kernel: 16 = weight-streaming form, 128 = 128 x 128 tile form.
+ * N % 32 == 0 and K % 32 == 0.  The grid covers the worst-case number of blocks; blocks past num_tokens_post_pad[0] return. */
+int sgl_mi355_moe_grouped_gemm(const void* a, const void* w, void* out, const float* topk_weights, const int* sorted_token_ids,
+                               const int* experts_ids, const int* num_tokens_post_pad, int64_t num_pairs, int a_rows_div,
+                               int num_experts, int N, int K, int block_size, int epilogue, int dtype, void* stream);
+/* Which form fused_experts picks (host logic only; the reference's counterpart is try_get_optimal_moe_config,
+ * fused_moe.py:1446-1455): 0 = streaming (block_size 16) up to 8 pairs per expert (measured: profiles/moe_sweep.csv),
+ * 1 = tile (block_size 128). */
+int sgl_mi355_moe_gemm_form(int64_t num_pairs, int num_experts, int N, int K);
+/* moe_sum_reduce (fused_moe.py:1299-1388, 1586-1613): out[t] = T(routed_scaling_factor * sum_j y[t][j]), f32, j ascending;
+ * y [T, topk, hidden], out [T, hidden] (may be the layer's input).  topk_ids (optional): j whose id is outside
+ * [0, num_experts) is skipped and its row of y never read. */
+int sgl_mi355_moe_sum_reduce(const void* y, void* out, const int* topk_ids, int num_tokens, int topk, int hidden, int num_experts,
+                             float routed_scaling_factor, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

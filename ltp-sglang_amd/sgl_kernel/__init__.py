@@ -79,6 +79,7 @@ from .kvcache import (
     set_mla_kv_buffer,
     write_req_to_token,
 )
+from .moe import moe_align_block_size, moe_gemm_form, moe_grouped_gemm, moe_sum_reduce, topk_softmax
 from .torch_ops import register as register_torch_ops
 
 register_torch_ops()   # torch.ops.sgl_kernel.<op>: what the reference's Python wrappers call (gemm.py:34-42)
